@@ -16,8 +16,23 @@ Transports (`--transport`):
   asgi  the full ASGI app (Prometheus + rate-limit middleware, routing, auth, validation, cache,
         JSON) driven in-process by a minimal ASGI client — no sockets; the engine runs in its own
         process on the rank's GPU (one app + engine per rank).
-  both  (default) tcp for the headline, then asgi, then asgi with the prefix cache off; the last two
-        are reported in `detail.asgi` / `detail.prefix_cache_off`.
+  both  (the default with `--full`) tcp for the headline, then asgi, then asgi with the prefix cache
+        off; the last two are reported in `detail.asgi` / `detail.prefix_cache_off`.
+
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: the tcp pass.
+`--full` adds everything else the benchmark measures (the asgi passes above); the headline keys mean
+the same in both.
+
+`--dump-outputs DIR` writes replies of the timed path that are the same in every run
+(write_outputs()).  The timed steps themselves cannot give that: a request's bf16 rounding depends on
+the batches it is scheduled into, which follow the arrival timing, and with random weights the greedy
+decode picks among nearly tied logits, so two runs of one build returned only 44 of 256 last-step
+replies identical.  So after the timed steps, once the engine is idle, the queries of the last timed
+step (request number W + K - 1) of a fixed sample of 64 clients go through the same path again, over
+one connection and one at a time: each is then prefilled and decoded on its own, whatever happened
+before.  The first priming request is sent on its own for the same reason (the KV blocks of the
+instruction template, which every request shares).  With more than one engine replica the router's
+choice of replica is not fixed.
 
 Load (`--load`): `closed` (default) C clients per GPU, each sending its next distinct cache-miss
 query as soon as the previous reply arrives (BASELINE.md's concurrency-N method); `open` Poisson
@@ -26,6 +41,8 @@ arrivals at `--rate` req/s per GPU (latency under an arrival rate instead of a f
 (fake kubectl on PATH), and /metrics scrapes, with per-class counts and p50s in `detail`.
 
   python bench.py                                   # 1 GPU, defaults (driver form)
+  python bench.py --full                            # plus the asgi and prefix-cache-off passes
+  python bench.py --dump-outputs out/               # plus out/*.npy: reproducible replies
   python bench.py --gpus 8                          # spawns 8 ranks itself (torch.distributed.run)
   torchrun --nproc-per-node 8 bench.py --gpus 8     # driver form for N > 1
   python bench.py --transport asgi                  # in-process transport only
@@ -92,6 +109,37 @@ def prompt_len(model: str) -> int:
     return len(before + tok.encode(PROMPT_PREFIX) + tok.encode(make_query(0, 0, 0) + PROMPT_SUFFIX) + after)
 
 
+DUMP_CLIENTS = 64   # --dump-outputs: clients whose last-step query is replayed (a fixed, seeded sample)
+DUMP_WIDTH = 256    # bytes kept per reply (16 new tokens decode to far fewer)
+
+
+def dump_queries(args, rank, C):
+    """--dump-outputs: the queries of the last timed step (request number W + K - 1) of a fixed,
+    seeded sample of the rank's clients, the same in every run.  Marked `dump`, so that the
+    service's response cache cannot answer with the timed phase's reply."""
+    last = args.warmup + args.steps - 1
+    ids = sorted(random.Random(0).sample(range(C), min(C, DUMP_CLIENTS)))
+    return [b'{"query":' + json.dumps("dump " + make_query(rank, last, i)).encode() + b"}" for i in ids]
+
+
+def write_outputs(out_dir: str, replies_by_rank) -> None:
+    """What a caller received for dump_queries(): the `kubectl_command` of every reply, rows ordered
+    by (rank, sampled client).  `kubectl_command_bytes.npy` holds the UTF-8 bytes of each command as
+    float32, zero-padded to DUMP_WIDTH; `kubectl_command_len.npy` the byte length of each."""
+    import numpy as np
+    raws = [raw for replies in replies_by_rank for raw in replies]
+    text = np.zeros((len(raws), DUMP_WIDTH), dtype=np.float32)
+    length = np.zeros((len(raws),), dtype=np.float32)
+    for j, raw in enumerate(raws):
+        b = json.loads(raw)["kubectl_command"].encode()
+        length[j] = len(b)
+        b = b[:DUMP_WIDTH]
+        text[j, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "kubectl_command_bytes.npy"), text)
+    np.save(os.path.join(out_dir, "kubectl_command_len.npy"), length)
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -112,7 +160,15 @@ def parse_args(argv=None):
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--in-process", action="store_true",
                     help="asgi transport: run the engine in this process (default: its own process on the GPU)")
-    ap.add_argument("--transport", choices=["asgi", "tcp", "both"], default=os.environ.get("BENCH_TRANSPORT", "both"))
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the in-process asgi pass and the asgi "
+                         "pass with the prefix cache off (`--transport both`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, send the last timed step's queries of 64 sampled clients "
+                         "once more, one at a time, and write the replies as DIR/<name>.npy; closed-loop "
+                         "miss-only load")
+    ap.add_argument("--transport", choices=["asgi", "tcp", "both"], default=os.environ.get("BENCH_TRANSPORT") or None,
+                    help="default: tcp, or both with --full")
     ap.add_argument("--api-workers", type=int, default=int(os.environ.get("BENCH_API_WORKERS", 2)),
                     help="tcp: uvicorn API worker processes sharing the port, per GPU")
     ap.add_argument("--no-prefix-off-pass", action="store_true",
@@ -133,6 +189,13 @@ def parse_args(argv=None):
                          "--model llama3-70b --tp 8, --model mixtral-8x7b --tp 8 = EP 8); the server runs "
                          "DP = gpus / tp replicas, each a TP group of consecutive GPUs (tcp transport)")
     args = ap.parse_args(argv)
+    if args.transport is None:
+        args.transport = "both" if args.full else "tcp"
+    if args.dump_outputs and (args.load != "closed" or args.mix):
+        # only there has a client a last timed step with one fixed query
+        ap.error("--dump-outputs needs the closed-loop miss-only load (no --load open, no --mix)")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.tp < 1 or args.gpus % args.tp:
         ap.error(f"--tp {args.tp} must divide --gpus {args.gpus}")
     if args.tp > 1 and args.transport != "tcp":
@@ -365,6 +428,34 @@ async def scrape_engine_metrics(port):
     return out
 
 
+async def replay_tcp(args, rank, port, C):
+    """--dump-outputs, after the timed steps: wait until the engine has finished what the stopped
+    clients left in flight (its step counters stand still), then send dump_queries() one at a time
+    over one connection and return the replies."""
+    deadline = time.time() + 60
+    prev = None
+    while True:
+        m = await scrape_engine_metrics(port)
+        now = (m.get("decode_count"), m.get("prefill_count"))
+        if now == prev:
+            break
+        if time.time() > deadline:
+            raise RuntimeError("--dump-outputs: the engine did not go idle")
+        prev = now
+        await asyncio.sleep(0.3)
+    conn = HttpConn("127.0.0.1", port)
+    replies = []
+    try:
+        for body in dump_queries(args, rank, C):
+            status, raw = await conn.request("POST", "/kubectl-command", body)
+            if not reply_ok("miss", status, raw):
+                raise RuntimeError(f"--dump-outputs: bad reply {status}: {raw[:200]!r}")
+            replies.append(raw)
+    finally:
+        conn.close()
+    return replies
+
+
 def cpu_snapshot(pids_by_role):
     """CPU seconds (user + system) of every process of the server tree and of the load generators,
     keyed by process name (serve.py names its processes ka-api-<i> / ka-replica-<i> / ka-tp-<i>.<r>)."""
@@ -448,7 +539,10 @@ def run_tcp(args, rank, local, world, C, buckets, dist):
             # + hipGraph capture): prime every worker before timing anything
             async def prime():
                 conns = [HttpConn("127.0.0.1", port) for _ in range(4 * args.api_workers * world)]
-                rs = await asyncio.gather(*[c.request("POST", "/kubectl-command", b'{"query":"prime %d"}' % j)
+                # one request on its own first: the instruction template's KV blocks, which every later
+                # request shares, are then computed by the same one-sequence prefill in every run
+                rs = [await conns[0].request("POST", "/kubectl-command", b'{"query":"prime"}')]
+                rs += await asyncio.gather(*[c.request("POST", "/kubectl-command", b'{"query":"prime %d"}' % j)
                                             for j, c in enumerate(conns)])
                 if args.mix:   # hot queries for the hit class, inserted through ONE worker: the other
                     for r in range(world):   # workers' hits prove the cache is shared
@@ -507,12 +601,19 @@ def run_tcp(args, rank, local, world, C, buckets, dist):
             _barrier(dist)   # every rank's clients are done before rank 0 stops the server
         if errors:
             raise RuntimeError("bad replies: %s" % errors[:3])
+        replies = []
+        if args.dump_outputs:
+            for r in range(world):   # one rank after the other: one request in the engine at a time
+                if r == rank:
+                    replies = asyncio.run(replay_tcp(args, rank, port, C))
+                if world > 1:
+                    _barrier(dist)
         d = {k: m1.get(k, 0.0) - m0.get(k, 0.0) for k in m1}
         st = {"decode_steps": int(d.get("decode_count", 0)), "decode_ms": d.get("decode_sum", 0.0) * 1e3,
               "prefill_steps": int(d.get("prefill_count", 0)), "prefill_ms": d.get("prefill_sum", 0.0) * 1e3,
               "queue_wait_ms_mean": round(d.get("qwait_sum", 0.0) * 1e3 / max(1.0, d.get("qwait_count", 0.0)), 2),
               "cpu_cores": cpu_util(c0, c1, elapsed)}
-        return elapsed, lat, st, t_build, None
+        return elapsed, lat, st, t_build, None, replies
     finally:
         if srv is not None:
             if srv.poll() is None:
@@ -574,6 +675,7 @@ def run_asgi(args, rank, local, world, C, buckets, dist, prefix_caching=True):
     logging.getLogger("app").setLevel(logging.WARNING)
     app = create_app(settings, backend=backend)
     lat = {"miss": [], "hit": [], "exec": []}
+    replies = []   # --dump-outputs
     headers = [(b"host", b"bench"), (b"content-type", b"application/json")]
 
     async def asgi_call(method, path, body: bytes):
@@ -619,6 +721,9 @@ def run_asgi(args, rank, local, world, C, buckets, dist, prefix_caching=True):
 
     async def run():
         await backend.start()
+        if args.dump_outputs:   # as run_tcp's prime(): the shared template blocks from one lone request
+            st, raw = await asgi_call("POST", "/kubectl-command", b'{"query":"prime"}')
+            assert st == 200, raw
         if args.mix:
             for j in range(32):
                 st, raw = await asgi_call("POST", "/kubectl-command", b'{"query":' + json.dumps(
@@ -688,9 +793,21 @@ def run_asgi(args, rank, local, world, C, buckets, dist, prefix_caching=True):
         st1 = await sync_barrier()
         el = time.perf_counter() - t0
         state["stop"] = True
+        if args.dump_outputs:   # as replay_tcp: the clients finish their requests, then one at a time
+            await asyncio.wait(tasks, timeout=120)
         for t in tasks:
             t.cancel()
         await asyncio.gather(*tasks, return_exceptions=True)
+        if args.dump_outputs and not errors:
+            for r in range(world):
+                if r == rank:
+                    for body in dump_queries(args, rank, C):
+                        status, raw = await asgi_call("POST", "/kubectl-command", body)
+                        if not reply_ok("miss", status, raw):
+                            raise RuntimeError(f"--dump-outputs: bad reply {status}: {raw[:200]!r}")
+                        replies.append(raw)
+                if world > 1:
+                    await asyncio.get_running_loop().run_in_executor(None, _barrier, dist)
         await backend.close()
         if errors:
             raise RuntimeError("bad replies: %s" % errors[:3])
@@ -709,7 +826,7 @@ def run_asgi(args, rank, local, world, C, buckets, dist, prefix_caching=True):
     else:
         elapsed, sample, st = asyncio.run(run())
     reply = json.loads(sample[0])["kubectl_command"] if sample else None
-    return elapsed, lat, st, t_build, (reply, backend.prompt_ids(make_query(0, 0, 0)))
+    return elapsed, lat, st, t_build, (reply, backend.prompt_ids(make_query(0, 0, 0))), replies
 
 
 def main():
@@ -748,7 +865,14 @@ def main():
         else:
             r = run_asgi(args, rank, local, world, C, buckets, dist, prefix_caching=name == "asgi")
             seq_len = len(r[4][1]) + args.max_new_tokens
-        results[name] = summarize(args, name, world, C, dist, r, seq_len)
+        results[name] = summarize(args, name, world, C, dist, r[:5], seq_len)
+        if args.dump_outputs and name == passes[0]:   # the headline pass's replies
+            replies = [r[5]]
+            if world > 1:
+                replies = [None] * world
+                dist.all_gather_object(replies, r[5])
+            if rank == 0:
+                write_outputs(args.dump_outputs, replies)
     if rank == 0:
         head = results[passes[0]]
         out = dict(head["out"])

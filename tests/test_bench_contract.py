@@ -39,9 +39,9 @@ def _run(args, world, launcher="torchrun"):
 
 @pytest.mark.parametrize("world,launcher", [(1, "self"), (2, "torchrun"), (2, "self")])
 def test_bench_prints_one_json_line(world, launcher):
-    out = _run([], world, launcher)
+    out = _run(["--full"], world, launcher)
     assert KEYS <= set(out)
-    # default: the headline over TCP through ONE server (DP = world replicas, one port), then the
+    # --full: the headline over TCP through ONE server (DP = world replicas, one port), then the
     # in-process ASGI transport and an ASGI pass with the prefix cache off, in detail
     d = out["detail"]
     assert d["transport"] == "tcp" and f"DP={world} replicas" in d["topology"]
@@ -54,6 +54,40 @@ def test_bench_prints_one_json_line(world, launcher):
     assert out["config"]["parallelism"] == f"dp{world}" and out["config"]["global_batch"] == 4 * world
     # value = total timed requests over the slowest rank's elapsed time
     assert out["value"] == pytest.approx(4 * world / (out["ms_per_step"] / 1e3), rel=0.02)
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """Without --full only the tcp headline pass runs; --dump-outputs replays the last timed step's
+    queries of the (here all 4) sampled clients one at a time and writes the replies as float32."""
+    import numpy as np
+    out = _run(["--steps", "2", "--dump-outputs", str(tmp_path / "dump")], 1)
+    assert KEYS <= set(out) and out["steps"] == 2 and out["dtype"] == "bf16"
+    d = out["detail"]
+    assert d["transport"] == "tcp" and "asgi" not in d and "prefix_cache_off" not in d
+    assert "asgi_value" not in out and out["tcp_value"] == out["value"] > 0
+    assert out["value"] == pytest.approx(2 * 4 / (2 * out["ms_per_step"] / 1e3), rel=0.02)
+    assert sorted(os.listdir(tmp_path / "dump")) == ["kubectl_command_bytes.npy", "kubectl_command_len.npy"]
+    text = np.load(tmp_path / "dump" / "kubectl_command_bytes.npy")
+    length = np.load(tmp_path / "dump" / "kubectl_command_len.npy")
+    assert text.dtype == np.float32 and text.shape == (4, 256)
+    assert length.dtype == np.float32 and length.shape == (4,) and (length > len("kubectl ")).all()
+    for row, n in zip(text, length):
+        assert bytes(row[:int(n)].astype(np.uint8)).startswith(b"kubectl ") and not row[int(n):].any()
+
+
+def test_bench_dump_outputs_needs_reproducible_inputs():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "3", "--warmup", "2", "--dump-outputs", "d"])
+    assert a.transport == "tcp" and bench.parse_args(["--full"]).transport == "both"
+    qs = bench.dump_queries(a, 0, 256)
+    assert qs == bench.dump_queries(a, 0, 256) and len(set(qs)) == len(qs) == bench.DUMP_CLIENTS
+    texts = [json.loads(q)["query"] for q in qs]
+    assert all(t.startswith("dump ") and t[5:] == bench.make_query(0, 4, int(t[5:].split(".")[0])) for t in texts)
+    assert len(bench.dump_queries(a, 0, 4)) == 4
+    for bad in (["--mix"], ["--load", "open", "--rate", "5"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(["--dump-outputs", "d"] + bad)
 
 
 def test_bench_gpus_must_match_world_size():

@@ -131,10 +131,14 @@ def test_multi_limits_stop_at_first_violation():
 
 # ---------------- dotenv / settings ----------------
 def test_dotenv_semantics(tmp_path):
-    text = open("/root/reference/.env-sample").read() if __import__("os").path.exists(
-        "/root/reference/.env-sample") else "CACHE_TTL=300      # seconds\n"
+    # the reference's sample file style: comment lines, blank lines, values with trailing comments
+    text = ("# Cache configuration\nCACHE_MAXSIZE=100  # Maximum number of cached items\n"
+            "CACHE_TTL=300      # seconds\n\n# Rate limiting\nRATE_LIMIT=10/minute  # per endpoint\n"
+            "OPENAI_BASE_URL=https://api.openai.com/v1  # Optional\n")
     vals = parse_dotenv(text)
     assert vals["CACHE_TTL"] == "300"
+    assert vals == {"CACHE_MAXSIZE": "100", "CACHE_TTL": "300", "RATE_LIMIT": "10/minute",
+                    "OPENAI_BASE_URL": "https://api.openai.com/v1"}
     p = tmp_path / ".env"
     p.write_text("export A=1 # c\nB='x # y'\nC=\"q\\nz\"\n# skip\nD=keep\n")
     env = {"D": "orig"}
