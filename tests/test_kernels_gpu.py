@@ -16,6 +16,7 @@ if not torch.cuda.is_available():  # collected on CPU with -m "not gpu" deselect
 
 from ai_agent_kubectl_amd import ops  # noqa: E402
 from ai_agent_kubectl_amd.ops import _hip, reference as ref  # noqa: E402
+from tests import attention_probes as ap  # noqa: E402
 
 DEV = "cuda"
 BF = torch.bfloat16
@@ -42,6 +43,21 @@ def test_rmsnorm(rows, hidden):
     y2 = ref.rmsnorm(x, w, 1e-5, residual=res2)
     close(res, res2, atol=1e-2)
     close(y, y2, atol=3e-2)
+
+
+def attn_close(got, q, kc, vc, bt, starts, ctx, scale, what):
+    """Attention output against the fp64 reference, relative to each (row, head)'s own magnitude: at
+    most 4 x the error of the bf16-emulating reference (tests/attention_probes.py).  With randn
+    inputs the output shrinks like 1 / sqrt(context), so `close`'s absolute tolerance is half the
+    signal at 2048 tokens; this bound is not.  starts None: decode (one query row per sequence)."""
+    if starts is None:
+        starts = torch.arange(q.shape[0] + 1, dtype=torch.int32, device=q.device)
+    want = ap.paged_reference(q, kc, vc, bt, starts, ctx, scale)
+    emu = ap.paged_reference(q, kc, vc, bt, starts, ctx, scale, emulate=True)
+    st = starts.tolist()
+    rows = torch.tensor([r for s, c in enumerate(ctx.tolist()) if c > 0 for r in range(st[s], st[s + 1])],
+                        device=q.device)
+    ap.assert_attention_close(got[rows], want[rows], emu[rows], what)
 
 
 def _cache(nb, hkv, bs=16, d=128):
@@ -94,7 +110,9 @@ def test_paged_decode(hq, hkv, ctx_lens):
     q = torch.randn(S, hq, 128, device=DEV, dtype=BF)
     ctx = torch.tensor(ctx_lens, dtype=torch.int32, device=DEV)
     scale = 128 ** -0.5
-    close(ops.attention_decode(q, kc, vc, bt, ctx, scale), ref.attention_decode(q, kc, vc, bt, ctx, scale), atol=2e-2)
+    got = ops.attention_decode(q, kc, vc, bt, ctx, scale)
+    close(got, ref.attention_decode(q, kc, vc, bt, ctx, scale), atol=2e-2)
+    attn_close(got, q, kc, vc, bt, None, ctx, scale, "test_paged_decode")
 
 
 @pytest.mark.parametrize("S,hq", [(80, 32), (160, 32), (160, 64)])
@@ -115,6 +133,7 @@ def test_paged_decode_large_batch_mixed_lengths(S, hq):
     got = ops.attention_decode(q, kc, vc, bt, ctx, 128 ** -0.5)
     want = ref.attention_decode(q, kc, vc, bt, ctx, 128 ** -0.5)
     close(got, want, atol=2e-2)
+    attn_close(got, q, kc, vc, bt, None, ctx, 128 ** -0.5, "test_paged_decode_large_batch_mixed_lengths")
     assert got[5].abs().max().item() == 0
 
 
@@ -168,6 +187,7 @@ def test_decode_attention_rope_fused(hq, hkv, reps, split, tight):
     want = ref.attention_decode(q, k2, v2, bt, ctx, scale)
     assert torch.equal(k1, k2) and torch.equal(v1, v2)
     close(got, want, atol=2e-2)
+    attn_close(got, q, k2, v2, bt, None, ctx, scale, "test_decode_attention_rope_fused")
     assert got[-1].abs().max().item() == 0
 
 
@@ -216,6 +236,8 @@ def test_decode_attention_rope_cascade(hq, hkv, ns, S):
     want = ref.attention_decode(q, k2, v2, bt, ctx, scale)
     close(got[:-1], want[:-1], atol=2e-2)
     close(got[:-1], plain[:-1], atol=2e-2)
+    attn_close(got, q, k2, v2, bt, None, ctx, scale, "test_decode_attention_rope_cascade")
+    attn_close(plain, q, k2, v2, bt, None, ctx, scale, "test_decode_attention_rope_cascade (plain)")
 
 
 @pytest.mark.parametrize("hq,hkv", [(32, 8), (64, 8), (8, 8)])
@@ -233,6 +255,7 @@ def test_paged_prefill(hq, hkv, qlens, ctxs):
     got = ops.attention_prefill(q, kc, vc, bt, starts, ctx, max(qlens), scale)
     want = ref.attention_prefill(q, kc, vc, bt, starts, ctx, scale)
     close(got, want, atol=2e-2)
+    attn_close(got, q, kc, vc, bt, starts, ctx, scale, "test_paged_prefill")
 
 
 def test_mixed_step_split_attention():
@@ -252,6 +275,7 @@ def test_mixed_step_split_attention():
                                 out=torch.empty_like(q))
     ops.attention_decode(q[:nd], kc, vc, bt[:nd], ctx[:nd], scale, out=out[:nd])
     close(out, ref.attention_prefill(q, kc, vc, bt, starts, ctx, scale), atol=2e-2)
+    attn_close(out, q, kc, vc, bt, starts, ctx, scale, "test_mixed_step_split_attention")
 
 
 def test_prefill_spike_forces_rescale():
@@ -268,6 +292,7 @@ def test_prefill_spike_forces_rescale():
     got = ops.attention_prefill(q, kc, vc, bt, starts, ctx, 40, 128 ** -0.5)
     want = ref.attention_prefill(q, kc, vc, bt, starts, ctx, 128 ** -0.5)
     close(got, want, atol=3e-2)
+    attn_close(got, q, kc, vc, bt, starts, ctx, 128 ** -0.5, "test_prefill_spike_forces_rescale")
 
 
 def test_silu_mul_and_embedding():
