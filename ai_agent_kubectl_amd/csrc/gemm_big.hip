@@ -702,7 +702,9 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args a) {
           for (int i = 0; i < 8; ++i) {
             const int n0 = tn * BN + 128 * wn + 16 * i + 4 * grp;
             uint32_t bits = 0xfu;
-            if (mrow) {   // n0 + vocab_offset is a multiple of 4: the 4 bits share one mask word
+            // n0 + vocab_offset is a multiple of 4: the 4 bits share one mask word.  Columns past N have
+            // no mask word (a row holds ceil((N + vocab_offset) / 32) of them): not loaded
+            if (mrow && n0 < a.N) {
               const int gb = n0 + a.vocab_offset;
               bits = (mrow[gb >> 5] >> (gb & 31)) & 0xfu;
             }

@@ -306,8 +306,25 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(bf16_t* __restrict__
   }
 }
 
+// mn % 4 != 0 (gemv_rows takes any N): one element per thread, the same slice order.  The vector
+// kernel reads float4 and stores uint2 at every i < mn, so it takes whole groups of 4 only.
+__global__ __launch_bounds__(256) void splitk_reduce_scalar_kernel(bf16_t* __restrict__ Y, const float* __restrict__ P,
+                                                                   int split, long mn) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < mn; i += (long)gridDim.x * blockDim.x) {
+    float s = 0.f;
+    for (int k = 0; k < split; ++k) s += P[(size_t)k * mn + i];
+    Y[i] = f2bf(s);
+  }
+}
+
 // Y[mn] = sum_k P[k][mn] in bf16 (also gemm_mfma.hip's EPI_P32 path with an output)
 extern "C" void ka_splitk_reduce_launch(bf16_t* Y, const float* P, int split, long mn, hipStream_t stream) {
+  if (mn % 4 != 0) {
+    long blocks = (mn + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(splitk_reduce_scalar_kernel, dim3((int)blocks), dim3(256), 0, stream, Y, P, split, mn);
+    return;
+  }
   long blocks = (mn / 4 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, Y, P, split, mn);
