@@ -17,6 +17,7 @@ if not torch.cuda.is_available():  # collected on CPU with -m "not gpu" deselect
 from ai_agent_kubectl_amd import ops  # noqa: E402
 from ai_agent_kubectl_amd.ops import _hip, reference as ref  # noqa: E402
 from tests import attention_probes as ap  # noqa: E402
+from tests import elementwise_probes as ep  # noqa: E402
 
 DEV = "cuda"
 BF = torch.bfloat16
@@ -41,7 +42,7 @@ def test_rmsnorm(rows, hidden):
     res2 = res.clone()
     y = ops.rmsnorm(x, w, 1e-5, residual=res)
     y2 = ref.rmsnorm(x, w, 1e-5, residual=res2)
-    close(res, res2, atol=1e-2)
+    assert torch.equal(res, res2)      # bf16(x + res): one fp32 add of two bf16 values, one rounding
     close(y, y2, atol=3e-2)
 
 
@@ -515,6 +516,8 @@ def test_moe_topk():
     w2, i2 = ref.moe_topk(lg, 2)
     assert torch.equal(i1.cpu().sort(1).values, i2.cpu().sort(1).values)
     close(w1.sort(1).values, w2.sort(1).values, atol=1e-5)
+    # and as (id, weight) pairs, slot by slot: sorted separately, swapped weights would pass
+    ep.assert_topk(w1, i1, *ep.topk_want(lg.cpu(), 2), "moe_topk pairs")
 
 
 @pytest.mark.parametrize("M", [1, 4, 5, 16, 33, 64, 128, 200, 256])
