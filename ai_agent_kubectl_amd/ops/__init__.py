@@ -316,17 +316,21 @@ def decode_persistent(h0: torch.Tensor, layer_ptrs: torch.Tensor, L: int, hq: in
                       scale: float, k_cache: torch.Tensor, v_cache: torch.Tensor, positions: torch.Tensor,
                       slot_mapping: torch.Tensor, block_table: torch.Tensor, ctx_lens: torch.Tensor,
                       cos_sin: torch.Tensor, ws: torch.Tensor, stamps: Optional[torch.Tensor] = None,
-                      tp=None) -> torch.Tensor:
+                      tp=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Every decoder layer of a decode step of B = 1 or 2 sequences in one persistent launch
     (csrc/decode_persistent.hip): h0 [B, H] bf16 embeddings -> the residual streams after the last
     layer [B, H] bf16.  layer_ptrs: int64 [L, 6] device pointers (wqkv, wo, w13, w2, ln1, ln2); caches
     [L, NB, hkv, ...]; positions / slot_mapping / ctx_lens [>= B]; block_table [>= B, max_blocks]
     (a 1-D table is the single sequence's).  tp: None, or (world, rank, xdata, xflag, xctr) of a tensor-
     parallel group (parallel/custom_allreduce.py OneShotAllReduce.pd_exchange): the row-parallel O /
-    down outputs are then all-reduced inside the kernel."""
+    down outputs are then all-reduced inside the kernel.  out: where to write the result (contiguous,
+    [B, H] bf16), a new tensor if None."""
     lib = require()
     B, H = h0.shape
-    out = torch.empty_like(h0)
+    if out is None:
+        out = torch.empty_like(h0)
+    elif out.shape != h0.shape or out.dtype != h0.dtype or out.device != h0.device or not out.is_contiguous():
+        raise ValueError("decode_persistent: out must be a contiguous tensor of h0's shape, dtype and device")
     bt_stride = block_table.stride(0) if block_table.dim() == 2 else block_table.shape[0]
     world, rank, xdata, xflag, xctr = tp if tp is not None else (0, 0, None, None, None)
     check(lib.ka_decode_persistent_tp(_p(out), _p(h0), _p(layer_ptrs), L, H, hq, hkv, I, float(eps), float(scale),

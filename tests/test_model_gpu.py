@@ -466,8 +466,10 @@ def test_persistent_decode_matches_kernel_chain_and_fp32(model, B, graphs, long_
     the error word clear — eagerly and as the captured bucket-B hipGraph.  long_ctx: a ~400-token
     context, past the tokens the attention leaders prefetch into their rings (the chunk loop's
     global-load path); at B = 2 the two sequences differ in length.  "/tp8": rank 0 of Llama-3-70B at
-    TP = 8 on a virtual communicator (H 8192, 8 q heads over 1 KV head: the GQA-8 attention scratch and
-    12-slot rings; its all-reduces are no-ops in the chain and the kernel alike)."""
+    TP = 8 on a virtual communicator (H 8192, 8 q heads over 1 KV head: the GQA-8 attention scratch, 16-slot
+    rings at B = 1 and 14-slot rings at B = 2 (pd_ring; the down rows' rings have 12 slots at B = 2); its
+    all-reduces are no-ops in the chain and the kernel alike).  Outside the appended slots the persistent
+    step leaves both caches bit-equal to what they were."""
     from ai_agent_kubectl_amd.engine.sequence import Sequence
     from ai_agent_kubectl_amd.models.llama import AttnMeta
     from ai_agent_kubectl_amd.parallel.comm import VirtualRankComm
@@ -527,6 +529,14 @@ def test_persistent_decode_matches_kernel_chain_and_fp32(model, B, graphs, long_
                 torch.testing.assert_close(kp[:, blk, :, off].float(), kc[:, blk, :, off].float(), atol=0.1, rtol=0.05)
                 torch.testing.assert_close(vp[:, blk, :, :, off].float(), vc[:, blk, :, :, off].float(), atol=0.1,
                                            rtol=0.05)
+            # everywhere else the persistent step wrote nothing: the pre-step image with the appended
+            # entries pasted in is the post-step cache
+            k_img, v_img = r.k_cache.clone(), r.v_cache.clone()
+            for b in range(B):
+                slot = int(r._view("slots", B)[b])
+                k_img[:, slot // 16, :, slot % 16] = kp[:, slot // 16, :, slot % 16]
+                v_img[:, slot // 16, :, :, slot % 16] = vp[:, slot // 16, :, :, slot % 16]
+            assert torch.equal(kp, k_img) and torch.equal(vp, v_img)
             mask = r._view("mask", B) if r.mask_bits is not None else None
             tok = m.sample(h_p, r.mask_bits, mask)[:B].tolist()
             if graphs:   # the captured bucket-B graph runs the same kernel: the same tokens
