@@ -3,8 +3,12 @@
 The reference is an OpenAI *client* (`ChatOpenAI`, `/root/reference/app.py:117`).  Exposing the same
 wire format from this service lets existing OpenAI-speaking clients (including another copy of the
 reference pointed at `OPENAI_BASE_URL=http://<this host>/v1`, or this framework's own
-`LLM_BACKEND=openai`) use the MI355X engine directly.  Greedy decoding (temperature is accepted and
-ignored: the reference always used 0, app.py:109); `max_tokens` caps the completion.
+`LLM_BACKEND=openai`) use the MI355X engine directly.  `temperature` (0..2, default 0 = greedy, what
+the reference always used, app.py:109), `top_p` (0 < p <= 1), `top_k` (>= 0, 0 = off) and `seed` are
+honoured: above temperature 0 the engine samples by seeded Gumbel-max (csrc/sampling_stochastic.hip),
+and the same seed, prompt and parameters give the same completion whatever else is in the batch;
+without a seed every request draws its own.  Out-of-range values get 422; temperature > 0 on a
+tensor-parallel engine gets 400.  `max_tokens` caps the completion.
 Auth: when API_AUTH_KEY is set, `Authorization: Bearer <key>` or `X-API-Key: <key>`.
 """
 from __future__ import annotations
@@ -26,7 +30,10 @@ class ChatRequest(BaseModel):
     model: Optional[str] = None
     messages: List[ChatMessage] = Field(..., min_length=1)
     max_tokens: Optional[int] = Field(None, ge=1, le=4096)
-    temperature: Optional[float] = 0.0
+    temperature: Optional[float] = Field(0.0, ge=0, le=2)
+    top_p: Optional[float] = Field(1.0, gt=0, le=1)
+    top_k: Optional[int] = Field(0, ge=0)
+    seed: Optional[int] = None
     stream: Optional[bool] = False
 
 
@@ -55,7 +62,12 @@ def install(app, svc, settings) -> None:
         if req.stream:
             raise HTTPException(status_code=400, detail="stream=true is not supported")
         msgs = [m.model_dump() for m in req.messages]
-        text, finish, n_in, n_out = await backend.generate_chat(msgs, max_tokens=req.max_tokens or 64)
+        try:
+            text, finish, n_in, n_out = await backend.generate_chat(
+                msgs, max_tokens=req.max_tokens or 64, temperature=req.temperature or 0.0,
+                top_p=1.0 if req.top_p is None else req.top_p, top_k=req.top_k or 0, seed=req.seed)
+        except ValueError as e:   # a request this engine cannot serve (temperature > 0 under TP > 1)
+            raise HTTPException(status_code=400, detail=str(e))
         return {
             "id": "chatcmpl-" + uuid.uuid4().hex[:24], "object": "chat.completion", "created": int(time.time()),
             "model": req.model or settings.MODEL,

@@ -158,6 +158,10 @@ class LLMEngine:
 
     def submit(self, prompt_ids: List[int], params: SamplingParams, callback: Callable[[Sequence], None],
                forced_prefix: Optional[List[int]] = None) -> Sequence:
+        if params.temperature > 0 and self.runner.tp_size > 1:
+            # the vocab-parallel combine of sampled scores needs the per-row arrays on every rank: a
+            # worker-protocol change that is not made yet
+            raise ValueError("temperature > 0 is not supported with tensor parallelism (TP > 1)")
         seq = Sequence(prompt_ids=list(prompt_ids), params=params, callback=callback,
                        forced_prefix=list(forced_prefix or []))
         self._inbox.put(("add", seq))

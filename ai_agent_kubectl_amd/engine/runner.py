@@ -24,7 +24,7 @@ import torch
 
 from ..models.config import ModelConfig
 from .. import ops
-from ..models.llama import AttnMeta, LlamaModel
+from ..models.llama import SAMP_WORDS, AttnMeta, LlamaModel, SampleArrays
 
 logger = logging.getLogger("app.engine")
 from ..parallel.comm import LocalComm
@@ -132,6 +132,12 @@ class ModelRunner:
         self._pflip = 0
         self._h_fix = [torch.zeros(2 * B, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
         self.d_fix = torch.zeros(2 * B, dtype=torch.int32, device=self.device)
+        # the per-row sampling arrays (models/llama.py SampleArrays image, bmax rows) of a step with a
+        # temperature > 0 request, in buffers of their own: d_stage keeps its layout, and a step
+        # without such a request never touches them.  Two pinned images, reused two launches later
+        self.d_samp = torch.zeros(SAMP_WORDS * B, dtype=torch.int32, device=self.device)
+        self._h_samps = [torch.zeros(SAMP_WORDS * B, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
+        self._mflip = 0
         self.d_hdr = torch.zeros(HDR, dtype=torch.int32, device=self.device)
         self._h_hdrs = [torch.zeros(HDR, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
         self._hflip = 0
@@ -148,7 +154,7 @@ class ModelRunner:
         self.graphs: Dict[int, torch.cuda.CUDAGraph] = {}
         self.graph_pool = None
         self.stats = {"decode_steps": 0, "prefill_steps": 0, "graph_replays": 0, "decode_ms": 0.0,
-                      "prefill_ms": 0.0, "prefill_tokens": 0, "persistent_stalls": 0}
+                      "prefill_ms": 0.0, "prefill_tokens": 0, "persistent_stalls": 0, "sampled_steps": 0}
         # bucket -> the captured graph holds the persistent decode kernel (its error word must be read
         # back on every replay of that graph, whatever model.persistent says now)
         self.graph_persistent: Dict[int, bool] = {}
@@ -165,15 +171,55 @@ class ModelRunner:
     def _cascade(self, B: int) -> bool:
         return self.cascade_min_b > 0 and B >= self.cascade_min_b and self.device.type == "cuda"
 
-    def _decode_forward(self, B: int) -> None:
+    def _decode_forward(self, B: int, samp: Optional[SampleArrays] = None) -> None:
         meta = AttnMeta(positions=self._view("pos", B), slot_mapping=self._view("slots", B),
                         block_tables=self._view("bt", B), ctx_lens=self._view("ctx", B),
                         logits_indices=self.d_logits_idx[:B], is_decode=True,
                         shared_blocks=self._view("nsh", 1) if self._cascade(B) else None)
         h = self.model.forward(self._view("ids", B), meta, self.k_cache, self.v_cache)
         mask_idx = self._view("mask", B) if self.mask_bits is not None else None
-        tok = self.model.sample(h, self.mask_bits, mask_idx)
+        tok = self.model.sample(h, self.mask_bits, mask_idx, samp)
         self.d_out[:B].copy_(tok)
+
+    # ---- seeded sampling: steps that hold a request with temperature > 0 ----
+    @staticmethod
+    def _sampling(batch: Batch) -> bool:
+        return any(s.params.temperature > 0 for s in batch.seqs)
+
+    @staticmethod
+    def _pack_samp(seqs, h: np.ndarray, cap: int, ahead: int = 0) -> None:
+        """Fill a SampleArrays image of `cap` rows.  position: the count that picks the mask row
+        (num_generated + ahead), so a token is the same whether its step was chained, scheduled ahead
+        or recomputed after a preemption.  Rows of greedy requests and rows past the batch: temperature 0."""
+        h[:SAMP_WORDS * cap] = 0
+        f = h.view(np.float32)
+        f[2 * cap:3 * cap] = 1.0
+        sd = h[4 * cap:6 * cap].view(np.uint64)
+        for i, s in enumerate(seqs):
+            p = s.params
+            f[i] = max(0.0, float(p.temperature))
+            h[cap + i] = min(max(0, int(p.top_k)), 2 ** 31 - 1)
+            f[2 * cap + i] = float(p.top_p)
+            h[3 * cap + i] = s.num_generated + ahead
+            sd[i] = s.sample_seed
+
+    def _stage_samp(self, batch: Batch, rows: int, ahead: int = 0) -> Optional[SampleArrays]:
+        """The step's sampling arrays on the device (`rows` rows: the batch, then greedy padding), or
+        None when no request of `batch` samples: that step takes the greedy path untouched."""
+        if not self._sampling(batch):
+            return None
+        if self.tp_size > 1:
+            raise RuntimeError("sampling with temperature > 0 is not wired through the TP worker protocol")
+        self.stats["sampled_steps"] += 1
+        if rows > self.bmax:   # a synchronous step larger than the buffers (execute)
+            img = np.zeros(SAMP_WORDS * rows, dtype=np.int32)
+            self._pack_samp(batch.seqs, img, rows, ahead)
+            return SampleArrays.from_image(torch.from_numpy(img).to(self.device), rows, rows)
+        hb = self._h_samps[self._mflip]
+        self._mflip ^= 1
+        self._pack_samp(batch.seqs, hb.numpy(), self.bmax, ahead)
+        self.d_samp.copy_(hb, non_blocking=True)
+        return SampleArrays.from_image(self.d_samp, self.bmax, rows)
 
     def autotune(self) -> dict:
         """Pick hipBLASLt vs the hand-written decode GEMM per (bucket, N, K) on this model's weights."""
@@ -505,9 +551,12 @@ class ModelRunner:
             o = self._off["ids"]
             self.d_stage[o:o + Bp].index_copy_(0, self.d_fix[:nf].long(),
                                                self.d_out.index_select(0, self.d_fix[nf:2 * nf].long()))
-        self._launch_decode(Bp, n_copy)
+        samp = self._stage_samp(batch, Bp, ahead=1 if chained else 0)
+        self._launch_decode(Bp, n_copy, samp)
         ho[:B].copy_(self.d_out[:B], non_blocking=True)
-        eh = self._copy_err(persistent=self._persistent_step(Bp))
+        # a sampled step ran eagerly beside the bucket's graph: the model's current setting decides
+        # whether it launched the persistent kernel, not what the graph was captured with
+        eh = self._copy_err(persistent=self._persistent_step(Bp) if samp is None else self.model.persistent_ok(Bp))
         ev = None
         if self.device.type == "cuda":
             ev = torch.cuda.Event()
@@ -538,7 +587,7 @@ class ModelRunner:
         self.model.mark_layer = max(0, self.cfg.num_layers - self.lookahead_layers)
         self.model.mark_event = None
         try:
-            tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens)
+            tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens, self._stage_samp(batch, S))
         finally:
             self.model.mark_layer = -1
         progress, self.model.mark_event = self.model.mark_event, None
@@ -652,11 +701,14 @@ class ModelRunner:
         self.stats["decode_steps"] += 1
         return ho[:B].tolist()
 
-    def _launch_decode(self, Bp: int, n_copy: int) -> None:
+    def _launch_decode(self, Bp: int, n_copy: int, samp: Optional[SampleArrays] = None) -> None:
         if self.tp_size > 1:
             self.comm.broadcast(self.d_stage[:n_copy], src=0)
-        g = self.graphs.get(Bp)
-        if g is not None:
+        # the captured graphs end in the greedy sampler: a step with a sampling request runs eagerly
+        g = self.graphs.get(Bp) if samp is None else None
+        if samp is not None:
+            self._decode_forward(Bp, samp)
+        elif g is not None:
             g.replay()
             self.stats["graph_replays"] += 1
         else:
@@ -743,7 +795,7 @@ class ModelRunner:
         return (buf, nf) if with_fix else buf
 
     def _run_prefill(self, buf: torch.Tensor, T: int, S: int, max_q: int, nc: int = 0, nd: int = 0,
-                     t_real: int = 0) -> torch.Tensor:
+                     t_real: int = 0, samp: Optional[SampleArrays] = None) -> torch.Tensor:
         mb = self.max_blocks
         if nc:
             n = buf.shape[0]
@@ -759,7 +811,7 @@ class ModelRunner:
                         is_decode=False, q_starts=q_starts, max_q_len=max_q, num_decode=nd,
                         num_tokens=t_real or T)
         h = self.model.forward(ids, meta, self.k_cache, self.v_cache)
-        return self.model.sample(h, self.mask_bits, mask if self.mask_bits is not None else None)
+        return self.model.sample(h, self.mask_bits, mask if self.mask_bits is not None else None, samp)
 
     # ------------------------------------------------------------------------------------------
     def _bcast_header(self, kind: int, a: int = 0, b: int = 0, c: int = 0, d: int = 0, e: int = 0,
@@ -799,7 +851,8 @@ class ModelRunner:
             n_copy = self._off["bt"] + Bp * self.max_blocks
             self._bcast_header(KIND_DECODE, Bp, n_copy)
             self.d_stage[:n_copy].copy_(self.h_stage[:n_copy], non_blocking=True)
-            self._launch_decode(Bp, n_copy)
+            samp = self._stage_samp(batch, Bp)
+            self._launch_decode(Bp, n_copy, samp)
             self.h_out[:B].copy_(self.d_out[:B], non_blocking=True)
             eh = self._copy_err()
             if self.device.type == "cuda":
@@ -816,7 +869,7 @@ class ModelRunner:
         buf = torch.from_numpy(host).to(self.device, non_blocking=False)
         if self.tp_size > 1:
             self.comm.broadcast(buf, src=0)
-        tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens)
+        tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens, self._stage_samp(batch, S))
         eh = self._copy_err()
         out = tok.cpu().tolist()
         self._check_err(eh)

@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import enum
 import itertools
+import random
 import time
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional
@@ -27,6 +28,11 @@ class SamplingParams:
     max_new_tokens: int = 24
     ignore_eos: bool = False
     safe_decode: bool = True      # SAFE_DECODE token mask (engine/safe_decode.py)
+    # seeded sampling (csrc/sampling_stochastic.hip); the defaults are greedy decoding
+    temperature: float = 0.0      # 0 = greedy (top_k / top_p / seed then have no effect)
+    top_k: int = 0                # 0 = off
+    top_p: float = 1.0            # 1 = off
+    seed: Optional[int] = None    # None: a random 64-bit seed per sequence (Sequence.sample_seed)
 
 
 @dataclass(eq=False)   # identity semantics: `seq in list` / `remove` must not compare token lists
@@ -50,8 +56,11 @@ class Sequence:
     t_first_token: Optional[float] = None
     t_finish: Optional[float] = None
     ph_row: Optional[int] = None            # row of the in-flight step whose token is the PLACEHOLDER
+    sample_seed: int = 0                    # the 64 bits the sampling noise is keyed with (params.seed or random)
 
     def __post_init__(self):
+        seed = self.params.seed if self.params.seed is not None else random.getrandbits(64)
+        self.sample_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.n_forced = len(self.forced_prefix)
         if self.forced_prefix:
             # jump-forward: deterministic constrained tokens are appended to the prompt and also

@@ -118,13 +118,17 @@ class EngineLLM(LLMBackend):
                        for m in messages)
         return [tok.bos_id] + tok.encode(text)
 
-    async def generate_chat(self, messages, max_tokens: int = 64, safe: bool = False):
-        """Returns (text, finish_reason, prompt_tokens, completion_tokens)."""
+    async def generate_chat(self, messages, max_tokens: int = 64, safe: bool = False, temperature: float = 0.0,
+                            top_p: float = 1.0, top_k: int = 0, seed: Optional[int] = None):
+        """Returns (text, finish_reason, prompt_tokens, completion_tokens).  temperature 0 (the default)
+        decodes greedily; above it the engine samples (top_k / top_p cuts, `seed` makes it repeatable).
+        Raises ValueError for a request the engine cannot serve (temperature > 0 under TP > 1)."""
         if not self._started:
             await self.start()
         loop = asyncio.get_running_loop()
         fut: asyncio.Future = loop.create_future()
-        params = SamplingParams(max_new_tokens=max_tokens, ignore_eos=False, safe_decode=safe)
+        params = SamplingParams(max_new_tokens=max_tokens, ignore_eos=False, safe_decode=safe,
+                                temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=seed)
         ids = self.chat_ids(messages)
         seq = self.engine.submit(ids, params, lambda sq: loop.call_soon_threadsafe(_resolve, fut, sq),
                                  forced_prefix=self._forced if safe else None)

@@ -52,6 +52,27 @@ class AttnMeta:
     shared_blocks: Optional[torch.Tensor] = None   # decode: [1] leading blocks shared by every row (cascade)
 
 
+SAMP_WORDS = 6   # int32 words per row of a packed sampling image
+
+
+@dataclass
+class SampleArrays:
+    """Per-row sampling arrays of a step (ops.sample), [S] each on the logits' device."""
+    temperature: torch.Tensor          # fp32, 0 = greedy
+    top_k: torch.Tensor                # int32, 0 = off
+    top_p: torch.Tensor                # fp32, 1 = off
+    seed: torch.Tensor                 # int64 (the 64 seed bits)
+    position: torch.Tensor             # int32: tokens generated so far (the count that picks the mask row)
+
+    @classmethod
+    def from_image(cls, img: torch.Tensor, cap: int, n: int) -> "SampleArrays":
+        """Views of a packed int32 image [temperature | top_k | top_p | position | seed lo, hi pairs],
+        each section `cap` rows long (the seeds 2 * cap words), for its first `n` rows."""
+        return cls(temperature=img[0:n].view(torch.float32), top_k=img[cap:cap + n],
+                   top_p=img[2 * cap:2 * cap + n].view(torch.float32), position=img[3 * cap:3 * cap + n],
+                   seed=img[4 * cap:4 * cap + 2 * n].view(torch.int64))
+
+
 class LlamaModel:
     def __init__(self, cfg: ModelConfig, weights: Dict[str, torch.Tensor], comm=None, tp_rank: int = 0,
                  tp_size: int = 1, ep_rank: int = 0, ep_size: int = 1):
@@ -306,10 +327,19 @@ class LlamaModel:
         return ops.linear(hidden_last, self.W["lm_head"])
 
     def sample(self, hidden_last: torch.Tensor, mask_bits: Optional[torch.Tensor],
-               mask_idx: Optional[torch.Tensor]) -> torch.Tensor:
+               mask_idx: Optional[torch.Tensor], samp: Optional["SampleArrays"] = None) -> torch.Tensor:
         """Greedy (temperature 0, app.py:109) next tokens under the SAFE_DECODE mask: [S] int32.
         Where it measured faster (ops.use_fused_lm_head), the LM head GEMM and the masked argmax are
-        one kernel and the logits are never written."""
+        one kernel and the logits are never written.
+        samp: the per-row sampling arrays of a step with at least one temperature > 0 request (TP = 1):
+        the logits are then written (unfused LM head) and every row goes through ops.sample, the
+        greedy requests' rows at temperature 0."""
+        if samp is not None:
+            if self.tp_size != 1:
+                raise RuntimeError("sampling with temperature > 0 is not wired through the TP worker protocol")
+            idx, _ = ops.sample(self.logits(hidden_last), mask_bits, mask_idx, samp.temperature, samp.top_k,
+                                samp.top_p, samp.seed, samp.position, vocab_offset=self.vocab_offset)
+            return idx
         lm = self.W["lm_head"]
         if ops.use_fused_lm_head(hidden_last, lm, self.vocab_offset):
             idx, val = ops.lm_head_argmax(hidden_last, lm, mask_bits, mask_idx, vocab_offset=self.vocab_offset)

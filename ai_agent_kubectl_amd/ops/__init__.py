@@ -299,6 +299,42 @@ def masked_argmax(logits: torch.Tensor, mask_bits: Optional[torch.Tensor], mask_
     return out_idx, out_val
 
 
+def sample(logits: torch.Tensor, mask_bits: Optional[torch.Tensor], mask_idx: Optional[torch.Tensor],
+           temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor,
+           position: torch.Tensor, vocab_offset: int = 0, return_cut: bool = False):
+    """Seeded temperature / top-k / top-p token per row among the tokens mask row `mask_idx[r]` allows
+    (csrc/sampling_stochastic.hip; semantics: ops/reference.py `sample`).  Per-row arrays: temperature
+    fp32 (0 = the greedy `masked_argmax`, bit for bit), top_k int32 (0 = off), top_p fp32 (1 = off),
+    seed int64 (its 64 bits), position int32 (tokens the sequence has generated so far).  The noise is
+    indexed by the global token id (local + vocab_offset) and the winning score is returned, so the
+    (val, idx) pairs of vocab-parallel slices merge with `argmax_combine`.
+    -> (idx int32, val fp32) [+ (cut fp32, kept int32) with return_cut]."""
+    if _ref(logits):
+        return ref.sample(logits, mask_bits, mask_idx, temperature, top_k, top_p, seed, position, vocab_offset,
+                          return_cut=return_cut)
+    lib = require()
+    B, V = logits.shape
+    dev = logits.device
+    for name, t, dt in (("temperature", temperature, torch.float32), ("top_k", top_k, torch.int32),
+                        ("top_p", top_p, torch.float32), ("seed", seed, torch.int64),
+                        ("position", position, torch.int32)):
+        if t is None or t.dtype != dt or t.shape != (B,) or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"sample: {name} must be a contiguous {dt} [{B}] tensor on {dev}")
+    if not logits.is_contiguous() or logits.dtype != torch.bfloat16:
+        raise ValueError("sample: logits must be contiguous bf16 [rows, vocab]")
+    out_idx = torch.empty(B, dtype=torch.int32, device=dev)
+    out_val = torch.empty(B, dtype=torch.float32, device=dev)
+    cut = torch.empty(B, dtype=torch.float32, device=dev) if return_cut else None
+    kept = torch.empty(B, dtype=torch.int32, device=dev) if return_cut else None
+    words = mask_bits.shape[1] if mask_bits is not None else 0
+    slices = lib.ka_argmax_slices(B, V)   # small batches: the row is split over workgroups
+    ws = (torch.empty(lib.ka_sample_ws_words(B, slices), dtype=torch.int32, device=dev) if slices > 1 else None)
+    check(lib.ka_sample(_p(out_idx), _p(out_val), _p(cut), _p(kept), _p(logits), _p(mask_bits),
+                        _p(mask_idx) if mask_bits is not None else None, _p(temperature), _p(top_k), _p(top_p),
+                        _p(seed), _p(position), B, V, words, int(vocab_offset), _p(ws), slices, _stream()), "sample")
+    return (out_idx, out_val, cut, kept) if return_cut else (out_idx, out_val)
+
+
 def argmax_combine(vals: torch.Tensor, idxs: torch.Tensor) -> torch.Tensor:
     """TP vocab-parallel greedy combine: vals / idxs [ranks, S] (every rank's best value and global token
     id) -> [S] int32 id of the largest value, the lowest id on ties (csrc/sampling.hip)."""

@@ -144,3 +144,114 @@ def argmax_combine(vals: torch.Tensor, idxs: torch.Tensor) -> torch.Tensor:
     big = torch.iinfo(torch.int32).max
     cand = torch.where(v == best, idxs.to(torch.int64), torch.full_like(idxs, big, dtype=torch.int64))
     return cand.min(dim=0).values.to(torch.int32)
+
+
+# ---- seeded temperature / top-k / top-p sampling (csrc/sampling_stochastic.hip) ----
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _mix64(z):
+    """splitmix64's finaliser on numpy uint64 arrays (arithmetic modulo 2^64)."""
+    import numpy as np
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def sample_noise_u(seed: int, position: int, gids) -> "np.ndarray":
+    """u in (0, 1) per global token id, float64 holding the exact fp32 value the kernel computes:
+    key = mix(seed + (position + 1) * G); z = mix(key + (gid + 1) * G); u = (2 * (z >> 41) + 1) * 2^-24."""
+    import numpy as np
+    g = np.uint64(_GOLDEN)
+    s = np.asarray([int(seed) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64)
+    key = _mix64(s + np.asarray([int(position) + 1], dtype=np.uint64) * g)
+    z = _mix64(key + (np.asarray(gids, dtype=np.uint64) + np.uint64(1)) * g)
+    return (2.0 * (z >> np.uint64(41)).astype(np.float64) + 1.0) * 2.0 ** -24
+
+
+def _bf16_key(x: torch.Tensor) -> torch.Tensor:
+    """Order-preserving 16-bit key (int64) of bf16 values: larger value <=> larger key; -0 counts as +0."""
+    b = x.to(torch.bfloat16).contiguous().view(torch.int16).long() & 0xFFFF
+    b = torch.where(b == 0x8000, torch.zeros_like(b), b)
+    return torch.where((b & 0x8000) != 0, b ^ 0xFFFF, b | 0x8000)
+
+
+def _bf16_key_value(k: torch.Tensor) -> torch.Tensor:
+    b = torch.where((k & 0x8000) != 0, k & 0x7FFF, k ^ 0xFFFF)
+    b = torch.where(b >= 0x8000, b - 0x10000, b)
+    return b.to(torch.int16).view(torch.bfloat16).float()
+
+
+def sample(logits, mask_bits, mask_idx, temperature, top_k, top_p, seed, position, vocab_offset: int = 0,
+           return_cut: bool = False, dtype=torch.float32, return_margins: bool = False):
+    """Gumbel-max sampling per row among the tokens mask row `mask_idx[r]` allows (-1 = all):
+    temperature 0 = `masked_argmax`; top_k = k keeps the logits >= the min(k, allowed)-th largest
+    (ties stay); top_p = p then keeps the logits >= the first value (walking the distinct values
+    downwards) at which the mass of exp((l - max) / T) reaches p x the total; the token is the argmax
+    of l / T - log(-log(u)) over the kept set (lowest id on ties), u = `sample_noise_u`.
+    -> (idx int32, val fp32) [+ (cut fp32, kept int32) with return_cut: the cut-off logit (-inf
+    without an active cut) and the number of tokens at or above it] [+ (gap, p_lo, p_hi) with
+    return_margins, in `dtype`: best minus second-best score (inf for temperature 0 or one kept
+    token), and how far p lies above the cumulative mass share just before the cut value / below the
+    share including it (inf without top-p)].  dtype: of the scores and masses (float64: ground truth)."""
+    idx, val = masked_argmax(logits, mask_bits, mask_idx, vocab_offset)
+    R, V = logits.shape
+    dev = logits.device
+    val = val.float().clone()
+    cut = torch.full((R,), float("-inf"), dtype=torch.float32, device=dev)
+    kept = torch.zeros(R, dtype=torch.int32, device=dev)
+    gap = torch.full((R,), float("inf"), dtype=dtype, device=dev)
+    p_lo = torch.full((R,), float("inf"), dtype=dtype, device=dev)
+    p_hi = torch.full((R,), float("inf"), dtype=dtype, device=dev)
+    gid = torch.arange(V, device=dev) + vocab_offset
+    if mask_bits is not None and mask_idx is not None:
+        words = mask_bits[:, gid // 32].long()
+        allowed_rows = ((words >> (gid % 32)) & 1).bool()
+    temps = temperature.float().cpu().tolist()
+    ks, ps = top_k.cpu().tolist(), top_p.float().cpu().tolist()
+    seeds, poss = seed.cpu().tolist(), position.cpu().tolist()
+    gid_np = gid.cpu().numpy()
+    for r in range(R):
+        T = temps[r]
+        mi = int(mask_idx[r]) if (mask_bits is not None and mask_idx is not None) else -1
+        allowed = allowed_rows[mi] if mi >= 0 else torch.ones(V, dtype=torch.bool, device=dev)
+        n_allowed = int(allowed.sum())
+        kept[r] = n_allowed
+        if not T > 0 or n_allowed == 0:
+            continue
+        l = logits[r].float()
+        keep = allowed
+        if ks[r] > 0 or ps[r] < 1:
+            la = l[allowed]
+            k = min(ks[r], n_allowed) if ks[r] > 0 else n_allowed
+            tau = torch.topk(la, k).values[-1]
+            if ps[r] < 1:
+                lk = la[la >= tau]
+                # a bf16 logit has 65,536 possible values: one mass bin per value, by its ordered key
+                key = _bf16_key(lk)
+                w = torch.exp((lk.to(dtype) - lk.max().to(dtype)) / T)
+                mass = torch.bincount(key, weights=w, minlength=65536).to(dtype)
+                vals = torch.bincount(key, minlength=65536).nonzero().squeeze(1).flip(0)   # distinct, downwards
+                cum = torch.cumsum(mass[vals], 0)
+                total = cum[-1]
+                j = int((cum >= ps[r] * total).nonzero()[0])
+                tau = _bf16_key_value(vals[j])
+                p_hi[r] = cum[j] / total - ps[r]
+                p_lo[r] = ps[r] - (cum[j - 1] / total if j > 0 else 0.0)
+            cut[r] = tau
+            keep = allowed & (l >= tau)
+            kept[r] = int(keep.sum())
+        u = torch.from_numpy(sample_noise_u(seeds[r], poss[r], gid_np)).to(dev)
+        g = -torch.log(-torch.log(u.to(dtype)))
+        score = (l.to(dtype) / T + g).masked_fill(~keep, float("-inf"))
+        i = int(torch.argmax(score))   # first index of the maximum
+        idx[r] = i + vocab_offset
+        val[r] = score[i]
+        if int(kept[r]) > 1:
+            gap[r] = score[i] - torch.topk(score, 2).values[1]
+    out = (idx, val)
+    if return_cut:
+        out += (cut, kept)
+    if return_margins:
+        out += (gap, p_lo, p_hi)
+    return out
