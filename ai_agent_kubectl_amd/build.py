@@ -52,7 +52,7 @@ def file_flags(src: str):
 
 
 def build_hip(force: bool = False, verbose: bool = False, extra_flags=(), out: str = "") -> str:
-    """out: another library path (an A/B build with `extra_flags`, e.g. -DKA_GM_SCHED=0, loaded only by
+    """out: another library path (an A/B build of an experiment with `extra_flags`, its -D or -mllvm options, loaded only by
     diagnostic runs: ops/_hip.py KA_HIP_LIB + KA_HIP_LIB_DIAG=1); its objects go next to it."""
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
     headers = glob.glob(os.path.join(CSRC, "*.h"))
@@ -85,7 +85,7 @@ def build_hip(force: bool = False, verbose: bool = False, extra_flags=(), out: s
 
 
 # Kernels whose k-loops read LDS fragments with inline-asm ds_reads and wait for them with a COUNTED
-# `s_waitcnt lgkmcnt(N)` (gemm_mfma.hip KA_GM_PIPE 2, gemm_big.hip): the count is only right if the
+# `s_waitcnt lgkmcnt(N)` (gemm_mfma.hip's ring kernel, gemm_big.hip): the count is only right if the
 # compiler puts no LGKM operation of its own (scalar/kernarg load, LDS access, flat access, message)
 # between those reads and the wait.  hipcc cannot see the asm, so a different compiler version or
 # scheduling choice could silently break it; check_lgkm_windows() re-verifies every build.

@@ -24,9 +24,10 @@
 // the step's tokens and falls back to the kernel chain).
 //
 // Weight streaming (Stream): each wave streams its rows 1 KB per LDS-DMA instruction (nt) through a
-// 16-slot LDS ring (no VGPRs held by bytes in flight), consumes two pieces per iteration against x in
-// LDS with v_dot2, and refills the slots; the next phase's first 16 pieces are issued between the
-// barrier arrival and the wait, so they stream while the grid synchronises.
+// 16-slot LDS ring (no VGPRs held by bytes in flight), used as two halves of 8 slots: it waits
+// vmcnt(0) for the half it is about to read, issues the next half, then consumes two pieces per
+// iteration against x in LDS with v_dot2.  The next phase's first half (8 pieces) is issued between
+// the barrier arrival and the wait, so it streams while the grid synchronises.
 #include "common.h"
 
 #include <algorithm>
@@ -35,35 +36,14 @@ namespace pd {
 
 #define KA_HD __host__ __device__ __forceinline__
 
-#ifndef KA_PD_RING
-#define KA_PD_RING 16
-#endif
-#ifndef KA_PD_ROT
-#define KA_PD_ROT 0   // measured: no effect (profiles/r4/persistent_decode)
-#endif
-#ifndef KA_PD_PREISSUE    // pieces of the next phase issued before a grid barrier's wait (the rest after it);
-#define KA_PD_PREISSUE 16 // (deferring all of the polling wave's pieces measured +2.5 us per barrier)
-#endif
-#ifndef KA_PD_NT
-#define KA_PD_NT 1
-#endif
-// LDS-DMA wait schedule of the weight streams.  LDS-DMA pieces of one wave do not always complete in
-// issue order (profiles/r5/gemm_big_clamp/), so only vmcnt(0) proves that a given piece has landed.
-//   1 (default, drained halves): the ring is two halves of RING / 2 slots; a wave waits vmcnt(0) for the
-//     half it is about to read, which at that moment is the only batch it has in flight (the next half
-//     is issued right after the wait, then dotted against while the first is consumed).
-//   0 (counted, rounds 4-5): RING - 2 pieces stay in flight across each counted wait; correct only
-//     under in-order completion, kept for A/B measurements.
-#ifndef KA_PD_SAFE
-#define KA_PD_SAFE 1
-#endif
 constexpr int NT = 512, NW = NT / 64, HD = 128, KBS = 16, NT_ = NT;
-// LDS-DMA ring slots (1 KB) per wave: KA_PD_RING (16) in every phase, except the down rows at B = 2,
+// LDS-DMA ring slots (1 KB) per wave: RING (16) in every phase, except the down rows at B = 2,
 // whose two act rows (2 x I bf16) take LDS the ring gives up there (12 slots, 96 KB per CU in flight;
 // 8 slots measured 16.4 us per layer for the down rows against 13.2 at B = 1)
-template <int B, int RG = KA_PD_RING>
+constexpr int RING = 16;
+template <int B, int RG = RING>
 constexpr int ring_down() { return B == 1 ? RG : (RG < 12 ? RG : 12); }
-static_assert((KA_PD_RING & (KA_PD_RING - 1)) == 0 && KA_PD_RING >= 2 && KA_PD_RING <= 16, "ring: a power of two <= 16");
+static_assert((RING & (RING - 1)) == 0 && RING >= 2 && RING <= 16, "ring: a power of two <= 16");
 constexpr int MAXB = 2;     // sequences per launch
 constexpr int XR_MAX_RANKS = 8, XR_MAX_WG = 256, XR_MAX_H = 16384;   // the in-kernel all-reduce's limits
 // The attention leader's scratch (aliases the x rows) for GR = 4 or 8 rows per KV group (GQA <= 4 /
@@ -275,13 +255,16 @@ KA_DEV float wave_total(float v) {
 // One wave's weight stream over `n` rows of length K (row(i) -> global row index): 1 KB per load
 // instruction (64 lanes x 16 B along K) by LDS-DMA (`buffer_load_dwordx4 ... lds`) into the wave's own
 // RING-slot LDS ring, so the bytes in flight cost no VGPRs (a register ring of the same depth spilled).
-// start() issues the first RING pieces (before the wait for the activations); run() takes the pieces
-// two at a time: waits for them (a static vmcnt: exactly RING pieces are always outstanding, the tail
-// re-reads the last chunk), reads both and their x chunks back from LDS under one lgkmcnt wait,
-// refills the two slots and dots.  Row results stay in registers (lane i holds row i: no store may sit
-// between the counted loads) and are returned by run(); the caller writes them after drain().
-// Every instruction between the counted loads is asm or VALU / SALU: a compiler-visible vector-memory
-// access there would get an s_waitcnt vmcnt(0) from hipcc — a drain of the whole ring.
+// The ring is two halves of RING / 2 slots.  LDS-DMA pieces of one wave do not always complete in
+// issue order (profiles/r5/gemm_big_clamp/), so only vmcnt(0) proves that a given piece has landed:
+// start() issues the first half (before the wait for the activations); run() waits vmcnt(0) for the
+// half it is about to read, at that moment the only batch in flight, issues the next half into the
+// other slots, then takes the landed pieces two at a time: reads both and their x chunks back from
+// LDS under one lgkmcnt wait and dots.  (The counted vmcnt(RING - 2) schedule of rounds 4-5 kept
+// RING - 2 pieces in flight across each wait and is correct only under in-order completion.)
+// Row results stay in registers (lane i holds row i) and are returned by run(); the caller writes
+// them after drain().  Every instruction of the loop is asm or VALU / SALU: a compiler-visible
+// vector-memory access there would get an s_waitcnt vmcnt(0) from hipcc before the next half is issued.
 // Row results of a stream: v[b] = the row's dot product with activation row b (lane i holds row i)
 template <int B>
 struct RowVals {
@@ -290,14 +273,14 @@ struct RowVals {
 
 template <int B, int RG, class RowFn>
 struct Stream {
-  static_assert(RG >= 2 && RG <= 16 && RG % 2 == 0, "ring slots: even, <= 16 (RG - 2 pieces in flight per wait)");
+  static_assert(RG >= 2 && RG <= 16 && RG % 2 == 0, "ring slots: even (two halves), <= 16");
   const bf16_t* W;
   int K, KC, total, lane;
   RowFn row;
   uint32_t nbytes;
   uint32_t ring;   // LDS byte address of this wave's ring (wave-uniform)
   int issued, ni, nc;   // pieces issued; row / chunk of the next piece to issue
-  int rot;              // every row is read from chunk `rot` on, wrapping (see make_stream)
+  int rot;              // first chunk of every row, wrapping: always 0 (see make_stream)
   KA_DEV void issue() {
     const uint32_t dst = __builtin_amdgcn_readfirstlane(ring + ((uint32_t)issued % (uint32_t)RG) * 1024u);
     // wave-uniform part of the byte offset (row start + chunk) -> soffset; the lane's 16 B -> voffset
@@ -309,42 +292,22 @@ struct Stream {
                                                                         (int)nbytes, 0x00020000);
     uint32_t keep;
     // nt: weights are read once per token (MI355X_MICROARCH.md nt-weights: issued -> landed -18 %)
-#if KA_PD_NT
-#define KA_PD_LDS_LOAD "buffer_load_dwordx4 %2, %3, %4 offen nt lds"
-#else
-#define KA_PD_LDS_LOAD "buffer_load_dwordx4 %2, %3, %4 offen lds"
-#endif
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t" KA_PD_LDS_LOAD "\n\t"
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen nt lds\n\t"
                  "s_mov_b32 m0, %0"
                  : "=&s"(keep)
                  : "s"(dst), "v"(off), "s"(rs), "s"(so)
                  : "memory");
-    if (++issued < total && ++nc == KC) {   // past the end: the last piece again (keeps the count static)
+    if (++issued < total && ++nc == KC) {   // next piece: the row's next chunk, then the next row
       nc = 0;
       ++ni;
     }
   }
-  static constexpr int HB = RG / 2;   // drained schedule: slots per half (one batch)
-  // the first N pieces (N < RG: the rest by top_up<N>() after the barrier wait, so the wait's polls
-  // queue behind fewer of the CU's own pieces).  Drained schedule: the first batch (half the ring)
-  template <int N = RG>
+  static constexpr int HB = RG / 2;   // slots per half (one batch)
+  // the first batch (half the ring)
   KA_DEV void start() {
     issued = ni = nc = 0;
     if (total <= 0) return;
-#if KA_PD_SAFE
     for (int r = 0; r < min(HB, total); ++r) issue();
-#else
-#pragma unroll
-    for (int r = 0; r < (N < RG ? N : RG); ++r) issue();
-#endif
-  }
-  template <int N>
-  KA_DEV void top_up() {
-#if !KA_PD_SAFE
-    if (total <= 0) return;
-#pragma unroll
-    for (int r = (N < RG ? N : RG); r < RG; ++r) issue();
-#endif
   }
   // xaddr: LDS byte address of activation row 0 (K bf16), row b at xaddr + b xstride
   KA_DEV RowVals<B> run(uint32_t xaddr, uint32_t xstride) {
@@ -370,7 +333,6 @@ struct Stream {
       }
     };
     int j = 0;
-#if KA_PD_SAFE
     // batches of HB pieces in alternating halves: wait for batch [j, j + n) (the only pieces in flight),
     // issue the next batch into the other half (read by the batch before, whose reads have completed),
     // then read and dot this one, two pieces at a time
@@ -380,86 +342,66 @@ struct Stream {
       for (int r = min(HB, total - j - n); r > 0; --r) issue();
       const int je = j + n;
       for (; j + 1 < je; j += 2) {
-#else
-    for (; j + 1 < total; j += 2) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RG - 2) : "memory");   // pieces j, j + 1 have landed
-#endif
-      const int xc = cc + rot >= KC ? cc + rot - KC : cc + rot;   // x chunks of pieces j, j + 1
-      const int xc1 = xc + 1 == KC ? 0 : xc + 1;
-      const uint32_t r0 = ring + ((uint32_t)j % (uint32_t)RG) * 1024u + lo16, r1 = ring + ((uint32_t)(j + 1) % (uint32_t)RG) * 1024u + lo16;
-      const uint32_t a0 = xaddr + (uint32_t)xc * 1024u + lo16, a1 = xaddr + (uint32_t)xc1 * 1024u + lo16;
-      uint4 w0, w1, x0[B], x1[B];
-      if constexpr (B == 1) {
-        asm volatile(
-            "ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\t"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(w0), "=&v"(w1), "=&v"(x0[0]), "=&v"(x1[0])
-            : "v"(r0), "v"(r1), "v"(a0), "v"(a1)
-            : "memory");
-      } else {
-        static_assert(B == 2, "rows per launch");
-        asm volatile(
-            "ds_read_b128 %0, %6\n\tds_read_b128 %1, %7\n\tds_read_b128 %2, %8\n\tds_read_b128 %3, %9\n\t"
-            "ds_read_b128 %4, %10\n\tds_read_b128 %5, %11\n\ts_waitcnt lgkmcnt(0)"
-            : "=&v"(w0), "=&v"(w1), "=&v"(x0[0]), "=&v"(x1[0]), "=&v"(x0[1]), "=&v"(x1[1])
-            : "v"(r0), "v"(r1), "v"(a0), "v"(a1), "v"(a0 + xstride), "v"(a1 + xstride)
-            : "memory");
+        const int xc = cc + rot >= KC ? cc + rot - KC : cc + rot;   // x chunks of pieces j, j + 1
+        const int xc1 = xc + 1 == KC ? 0 : xc + 1;
+        const uint32_t r0 = ring + ((uint32_t)j % (uint32_t)RG) * 1024u + lo16, r1 = ring + ((uint32_t)(j + 1) % (uint32_t)RG) * 1024u + lo16;
+        const uint32_t a0 = xaddr + (uint32_t)xc * 1024u + lo16, a1 = xaddr + (uint32_t)xc1 * 1024u + lo16;
+        uint4 w0, w1, x0[B], x1[B];
+        if constexpr (B == 1) {
+          asm volatile(
+              "ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\t"
+              "s_waitcnt lgkmcnt(0)"
+              : "=&v"(w0), "=&v"(w1), "=&v"(x0[0]), "=&v"(x1[0])
+              : "v"(r0), "v"(r1), "v"(a0), "v"(a1)
+              : "memory");
+        } else {
+          static_assert(B == 2, "rows per launch");
+          asm volatile(
+              "ds_read_b128 %0, %6\n\tds_read_b128 %1, %7\n\tds_read_b128 %2, %8\n\tds_read_b128 %3, %9\n\t"
+              "ds_read_b128 %4, %10\n\tds_read_b128 %5, %11\n\ts_waitcnt lgkmcnt(0)"
+              : "=&v"(w0), "=&v"(w1), "=&v"(x0[0]), "=&v"(x1[0]), "=&v"(x0[1]), "=&v"(x1[1])
+              : "v"(r0), "v"(r1), "v"(a0), "v"(a1), "v"(a0 + xstride), "v"(a1 + xstride)
+              : "memory");
+        }
+#pragma unroll
+        for (int b = 0; b < B; ++b) acc[b] = dot8(w0, x0[b], acc[b]);
+        finish();
+#pragma unroll
+        for (int b = 0; b < B; ++b) acc[b] = dot8(w1, x1[b], acc[b]);
+        finish();
       }
-#if !KA_PD_SAFE
-      issue();   // both slots are free again: refill them RG pieces ahead
-      issue();
-#endif
+      if (j < je) {   // an odd batch: its last piece
+        const uint32_t r0 = ring + ((uint32_t)j % (uint32_t)RG) * 1024u + lo16;
+        const uint32_t a0 = xaddr + (uint32_t)(cc + rot >= KC ? cc + rot - KC : cc + rot) * 1024u + lo16;
+        uint4 w0, x0[B];
+        if constexpr (B == 1) {
+          asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)"
+                       : "=&v"(w0), "=&v"(x0[0])
+                       : "v"(r0), "v"(a0)
+                       : "memory");
+        } else {
+          asm volatile("ds_read_b128 %0, %3\n\tds_read_b128 %1, %4\n\tds_read_b128 %2, %5\n\ts_waitcnt lgkmcnt(0)"
+                       : "=&v"(w0), "=&v"(x0[0]), "=&v"(x0[1])
+                       : "v"(r0), "v"(a0), "v"(a0 + xstride)
+                       : "memory");
+        }
 #pragma unroll
-      for (int b = 0; b < B; ++b) acc[b] = dot8(w0, x0[b], acc[b]);
-      finish();
-#pragma unroll
-      for (int b = 0; b < B; ++b) acc[b] = dot8(w1, x1[b], acc[b]);
-      finish();
-    }
-#if KA_PD_SAFE
-    if (j < je) {   // an odd batch: its last piece
-#else
-    if (j < total) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RG - 1) : "memory");
-#endif
-      const uint32_t r0 = ring + ((uint32_t)j % (uint32_t)RG) * 1024u + lo16;
-      const uint32_t a0 = xaddr + (uint32_t)(cc + rot >= KC ? cc + rot - KC : cc + rot) * 1024u + lo16;
-      uint4 w0, x0[B];
-      if constexpr (B == 1) {
-        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&v"(w0), "=&v"(x0[0])
-                     : "v"(r0), "v"(a0)
-                     : "memory");
-      } else {
-        asm volatile("ds_read_b128 %0, %3\n\tds_read_b128 %1, %4\n\tds_read_b128 %2, %5\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&v"(w0), "=&v"(x0[0]), "=&v"(x0[1])
-                     : "v"(r0), "v"(a0), "v"(a0 + xstride)
-                     : "memory");
+        for (int b = 0; b < B; ++b) acc[b] = dot8(w0, x0[b], acc[b]);
+        finish();
+        ++j;
       }
-#if !KA_PD_SAFE
-      issue();
-#endif
-#pragma unroll
-      for (int b = 0; b < B; ++b) acc[b] = dot8(w0, x0[b], acc[b]);
-      finish();
-#if KA_PD_SAFE
-      ++j;
-#endif
     }
-#if KA_PD_SAFE
-    }
-#endif
     return mine;
   }
   KA_DEV void drain() const { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 };
-// gw: the wave's grid-wide index.  Each wave starts its rows at chunk gw mod K/512: waves that leave
-// a grid barrier together would otherwise all read the same 1-KB column of their rows at once —
-// addresses equal modulo the row pitch, the same few HBM channels.
+// Every wave reads its rows from chunk 0 on: rot = 0 (starting each wave at a chunk of its own, so that
+// waves leaving a grid barrier together read different columns, measured no effect:
+// profiles/r4/persistent_decode).  The member and its wraps fold away, but taking them out of the source
+// changes the kernel's register allocation, so that needs a measurement of its own.
 template <int B, int RG, class RowFn>
-KA_DEV Stream<B, RG, RowFn> make_stream(const bf16_t* W, int N, int K, int n, int lane, uint32_t ring, RowFn row, int gw) {
-  Stream<B, RG, RowFn> s{W, K, K / 512, n * (K / 512), lane, row, (uint32_t)N * (uint32_t)K * 2u, ring, 0, 0, 0,
-                         KA_PD_ROT ? gw % (K / 512) : 0};
+KA_DEV Stream<B, RG, RowFn> make_stream(const bf16_t* W, int N, int K, int n, int lane, uint32_t ring, RowFn row) {
+  Stream<B, RG, RowFn> s{W, K, K / 512, n * (K / 512), lane, row, (uint32_t)N * (uint32_t)K * 2u, ring, 0, 0, 0, 0};
   return s;
 }
 
@@ -723,10 +665,9 @@ __global__ __launch_bounds__(NT, 1) void decode_layers_kernel(Args a) {
     // The weight pieces of each phase are issued between the arrival and the wait of the barrier before
     // it: after the arrival (its vmcnt(0) would otherwise hold the arrival back until they landed),
     // in flight while the workgroup waits for the others.
-    auto sq = make_stream<B, RG>(Lw.wqkv, QKVN, H, nq, lane, ring, qkv_row, gw);
-    sq.template start<KA_PD_PREISSUE>();
+    auto sq = make_stream<B, RG>(Lw.wqkv, QKVN, H, nq, lane, ring, qkv_row);
+    sq.start();
     wait_grid(a.sync, ++nbar, G, err);
-    sq.template top_up<KA_PD_PREISSUE>();
     PD_STAMP(0);
     if (st && l > 0) st[(l - 1) * 16 + 12] = st[l * 16];   // the previous layer's barrier E ends here
     rmsnorm_rows_to_lds<B>(a, a.res, Lw.ln1, xs, xhb / 2, red);
@@ -745,7 +686,7 @@ __global__ __launch_bounds__(NT, 1) void decode_layers_kernel(Args a) {
     }
     // the O rows' weights are issued now: they stream while the group waits and attention runs
     PD_STAMP(2);
-    auto so = make_stream<B, RG>(Lw.wo, H, hq * HD, n_o, lane, ring, o_row, gw);
+    auto so = make_stream<B, RG>(Lw.wo, H, hq * HD, n_o, lane, ring, o_row);
     arrive(a.sync + SYNC_GROUP + 32 * grp);   // this workgroup's QKV rows are published
     so.start();
     if (leader) {
@@ -968,11 +909,10 @@ __global__ __launch_bounds__(NT, 1) void decode_layers_kernel(Args a) {
       }
     }
     PD_STAMP(6);
-    auto sg = make_stream<B, RG>(Lw.w13, 2 * I, H, 2 * ng, lane, ring, gu_row, gw);
+    auto sg = make_stream<B, RG>(Lw.w13, 2 * I, H, 2 * ng, lane, ring, gu_row);
     arrive(gcnt);
-    sg.template start<KA_PD_PREISSUE>();
+    sg.start();
     wait_grid(a.sync, ++nbar, G, err);
-    sg.template top_up<KA_PD_PREISSUE>();
     PD_STAMP(7);
     // ---- P4: norm + gate / up -> act ----
     rmsnorm_rows_to_lds<B>(a, a.res, Lw.ln2, xs, xhb / 2, red);
@@ -994,11 +934,10 @@ __global__ __launch_bounds__(NT, 1) void decode_layers_kernel(Args a) {
           st_sc1u(a.act + (size_t)b * I + wa0 + 2 * tid, reinterpret_cast<const uint32_t*>(ob)[b * 256 + tid]);
     }
     PD_STAMP(9);
-    auto sd = make_stream<B, RGD>(Lw.w2, H, I, no, lane, ring_d, own_row, gw);
+    auto sd = make_stream<B, RGD>(Lw.w2, H, I, no, lane, ring_d, own_row);
     arrive(gcnt);
-    sd.template start<KA_PD_PREISSUE>();
+    sd.start();
     wait_grid(a.sync, ++nbar, G, err);
-    sd.template top_up<KA_PD_PREISSUE>();
     PD_STAMP(10);
     // ---- P5: down rows -> residual ----
 #pragma unroll
@@ -1052,7 +991,7 @@ extern "C" size_t ka_decode_persistent_ws(int H, int hq, int hkv, int I) {
 
 // Weight-ring slots per wave for a geometry (gq = hq / hkv): 16, or 14 for two sequences of the GQA-8
 // geometry (their two 16-KB x rows leave room for no more)
-static int pd_ring(int gq, int B) { return gq > 4 ? (B == 1 ? 16 : 14) : KA_PD_RING; }
+static int pd_ring(int gq, int B) { return gq > 4 ? (B == 1 ? 16 : 14) : pd::RING; }
 
 // LDS layout of a B-sequence launch (see decode_layers_kernel); returns its bytes
 static int pd_layout(int B, int H, int hq, int I, pd::Args* a, int gq = 4) {
@@ -1176,7 +1115,7 @@ extern "C" int ka_decode_persistent_tp(void* h_out, const void* h0, const void* 
   const int rc = (int)hipGetLastError();
   if (rc != 0) return rc;
   if (B == 2 && pd_ring(hq / hkv, 2) == 14) return pd_launch<2, 14>(a, G, stream);
-  return B == 1 ? pd_launch<1, KA_PD_RING>(a, G, stream) : pd_launch<2, KA_PD_RING>(a, G, stream);
+  return B == 1 ? pd_launch<1, pd::RING>(a, G, stream) : pd_launch<2, pd::RING>(a, G, stream);
 }
 
 extern "C" int ka_decode_persistent(void* h_out, const void* h0, const void* layers, int L, int H, int hq, int hkv,

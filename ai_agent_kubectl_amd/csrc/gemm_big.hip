@@ -95,10 +95,9 @@ struct Args {
   // split tail (EPI_BF16 / SWIGLU / ADD): units [0, full) are whole tiles (full = a multiple of the
   // persistent grid); the tail_tiles tiles after them would leave most CUs idle in a last partial
   // round, so each is cut into tail_s K-slices run by different workgroups of ONE XCD.  Every wave
-  // of a slice publishes its fp32 quadrant (stores, the wave's own vmcnt(0), an agent-scope release),
-  // then adds to its quadrant's arrival counter; the wave whose add returns
-  // tail_s - 1 acquires at agent scope, sums the slices and runs the epilogue — no wait on other
-  // workgroups — and resets the counter for the next launch.
+  // of a slice publishes its fp32 quadrant (sc1 stores, the wave's own vmcnt(0)), then adds to its
+  // quadrant's arrival counter; the wave whose add returns tail_s - 1 sums the slices (sc1 loads) and
+  // runs the epilogue — no wait on other workgroups — and resets the counter for the next launch.
   int full, tail_s, tail_tiles, span;
   float* slab;   // [tail tile][tail_s slices][4 waves][64 accumulators][64 lanes] f32x4
   int* cnt;      // [tail tile][4 waves][arrivals, spare]
@@ -143,9 +142,6 @@ KA_DEV void ds_read16(bf16x8& dst, uint32_t addr) {
 // offset applies to both the LDS destination and the global address, so the lane's global offset is
 // pre-biased by -1024 P); P == 0 saves M0 and points it at the group, P == 3 restores it
 // LAST: the group's final piece (P == 3 of a 4-piece group; P == 1 of the 2-piece W group of TN 6)
-#ifndef KA_GB_CLAMP
-#define KA_GB_CLAMP 0     // diagnostic: rows past the end clamped to the last row (duplicate addresses)
-#endif
 template <int P, bool LAST>
 KA_DEV void dma16g(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, uint32_t lds_addr, uint32_t& keep) {
   static_assert(P > 0 || !LAST, "a group has at least two pieces");
@@ -174,10 +170,7 @@ KA_DEV void mfma_drain() { asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "mem
 // stale: 5/40 launches at M = 4096, N = 1152 with clamped duplicate rows, 1/80 at M = 2944, N = 6144 with
 // distinct rows), and a vmcnt(0) drain in the same places never failed (0/160, clamped rows included):
 // profiles/r5/gemm_big_clamp/.  So every LDS-DMA wait of this kernel is vmcnt(0), placed where the
-// only pieces in flight are the ones about to be read (KA_GB_DRAIN_B1 below).
-#ifndef KA_GB_DRAIN_B1
-#define KA_GB_DRAIN_B1 1  // 0: the old counted vmcnt(PIECES) at barrier #2 (unsafe, for A/B timing only)
-#endif
+// only pieces in flight are the ones about to be read (barrier #1 of `iter`).
 template <int N>
 KA_DEV void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 KA_DEV void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
@@ -205,27 +198,17 @@ KA_DEV void tile_of(int L, int tiles_m, int tiles_n, int gm, int& tm, int& tn) {
   tn = in / rows;
 }
 
-// 16-B store / load of the tail hand-off.  KA_GB_TAIL_MODE 0: plain accesses ordered by agent-scope
-// release / acquire fences; 1: sc1 (write-through) asm stores + the same fences; 2: sc1 asm stores and
-// loads, no fence (MI355X_MICROARCH.md hand-off table, row 1: one signalling lane per storing wave,
-// per-wave counter, the consumer told by the value its own add returned, all stores and loads sc1
-// 16 B, hipMalloc memory); 3: the sc1 loads of 2 after the fences of 1.  hipcc does not pad the
-// VMEM-store-data / VALU-write hazard around asm it cannot see, so the asm stores carry their own
-// wait states (without them a few lanes' data were corrupted: profiles/r4/gemm_big_tail/).
-// Round 5 full-matrix repeats (profiles/r5/gemm_big_tail_modes/): before the LDS-DMA drain fix, modes
-// 0 and 1 read stale data in some first launches; after it, all four modes were exact in every launch
-// (48 full checks each, after_drain/), so those failures were the DMA hazard.  Mode 2 stays the
-// default because it is the fastest: 2944 x 28672 SwiGLU 639-647 us against 650-667 for the fenced
-// modes, 78-83 against 90-113 us on an all-split shape.
-#ifndef KA_GB_TAIL_MODE
-#define KA_GB_TAIL_MODE 2
-#endif
+// 16-B store / load of the tail hand-off: sc1 (write-through) asm stores and sc1 asm loads, no fence
+// (MI355X_MICROARCH.md hand-off table, row 1: one signalling lane per storing wave, per-wave counter,
+// the consumer told by the value its own add returned, all stores and loads sc1 16 B, hipMalloc
+// memory).  hipcc does not pad the VMEM-store-data / VALU-write hazard around asm it cannot see, so
+// the asm stores carry their own wait states (without them a few lanes' data were corrupted:
+// profiles/r4/gemm_big_tail/).  The variants with agent-scope release / acquire fences (around plain
+// or sc1 accesses) were as exact once the LDS-DMA waits drained (profiles/r5/gemm_big_tail_modes/
+// after_drain/: 48 full checks each) and slower: 2944 x 28672 SwiGLU 650-667 us against 639-647,
+// 90-113 against 78-83 us on an all-split shape.
 template <int N>
 KA_DEV void st_slab(float* p, const f32x4 (&v)[N], const int (&q)[N]) {
-#if KA_GB_TAIL_MODE == 0
-#pragma unroll
-  for (int e = 0; e < N; ++e) *reinterpret_cast<f32x4*>(p + q[e] * 256) = v[e];
-#else
   // all stores in ONE asm statement followed by the wait states of the VMEM-store-data / VALU-write
   // hazard (hipcc cannot see the stores: with per-store statements and 2 wait states each, the
   // register allocator's next VALU write corrupted store data in a few lanes)
@@ -248,11 +231,9 @@ KA_DEV void st_slab(float* p, const f32x4 (&v)[N], const int (&q)[N]) {
         "v"(p + q[1] * 256), "v"(p + q[2] * 256), "v"(p + q[3] * 256), "v"(p + q[4] * 256), "v"(p + q[5] * 256),
         "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5])
         : "memory");
-#endif
 }
 template <int N>
 KA_DEV void ld_slab(f32x4 (&t)[N], const float* p, const int (&q)[N]) {
-#if KA_GB_TAIL_MODE >= 2   // 2: sc1 loads without fences; 3: sc1 loads after the fences of mode 1
 #pragma unroll
   for (int e = 0; e < N; ++e)
     asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(t[e]) : "v"(p + q[e] * 256) : "memory");
@@ -263,10 +244,6 @@ KA_DEV void ld_slab(f32x4 (&t)[N], const float* p, const int (&q)[N]) {
                  "+v"(t[6]), "+v"(t[7])::"memory");
   else
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5])::"memory");
-#else
-#pragma unroll
-  for (int e = 0; e < N; ++e) t[e] = *reinterpret_cast<const f32x4*>(p + q[e] * 256);
-#endif
 }
 
 // Tail slice hand-off of one wave's 128 x 128 quadrant (Args.full .. comment): every slice publishes
@@ -276,25 +253,16 @@ KA_DEV void ld_slab(f32x4 (&t)[N], const float* p, const int (&q)[N]) {
 // resets the counter for the next launch.  The accumulators are read at ONE place of the epilogue
 // (a second read, or summing into them, made hipcc move the whole tile into VGPRs and spill).
 KA_DEV bool tail_ticket(const Args& a, int tt, int w, int lane) {
-  // release at agent scope: this wave's slab stores are done and written back past its XCD's L2
-  // before its ticket (the slices of a tile are meant to share an XCD for speed, but placement is
-  // only observed, never promised).  The asm wait after the fence: MI355X_MICROARCH.md 'Compiler hazard'.
+  // this wave's sc1 slab stores are done and written through past its XCD's L2 before its ticket
+  // (the slices of a tile are meant to share an XCD for speed, but placement is only observed, never
+  // promised)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if KA_GB_TAIL_MODE != 2
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
   int* const c = a.cnt + (tt * 4 + w) * 2;
   int old = 0;
   if (lane == 0) old = __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   old = __builtin_amdgcn_readfirstlane(old);
   if (old != a.tail_s - 1) return false;
   if (lane == 0) __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // tile complete
-#if KA_GB_TAIL_MODE != 2
-  // acquire at agent scope before this wave reads the other slices' slabs
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
   return true;
 }
 
@@ -431,11 +399,7 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args a) {
         // them all to row N - 1 made 64-lane LDS-DMA pieces of duplicate addresses, and with them
         // other pieces' rows came out wrong in some launches (profiles/r5/gemm_big_clamp/)
         wrow = tn_ * BNT + row;
-#if KA_GB_CLAMP
-        wrow = min(wrow, a.N - 1);   // diagnostic: the old clamp
-#else
         if (wrow >= a.N) wrow %= a.N;
-#endif
       }
       if constexpr (GR) wrow += ge_ * a.N;   // expert ge_'s weights
       offA[j] = ((uint32_t)wrow * (uint32_t)a.K + ch) * 2u + kb + BIAS - (uint32_t)(j & 3) * 1024u;
@@ -448,11 +412,7 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args a) {
       // (rows past the end: distinct valid rows, as for W above)
       int xr;
       if constexpr (GR) xr = gr0_ + (row < gnr_ ? row : row % gnr_);
-#if KA_GB_CLAMP
-      else xr = min(m0_ + row, a.M - 1);   // diagnostic: the old clamp
-#else
       else xr = m0_ + row < a.M ? m0_ + row : (m0_ + row) % a.M;
-#endif
       offB[j] = ((uint32_t)xr * (uint32_t)a.ldx + ch) * 2u + kb + BIAS - (uint32_t)(j & 3) * 1024u;
     }
   };
@@ -492,21 +452,14 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args a) {
   constexpr int GPS = NQ / 4;        // groups per set
   constexpr int NG = 2 * GPS;        // groups per k-tile (32 at TN 8)
   constexpr int RW = NG - 4;         // F0(t + 1) read window: the k-tile's last 4 groups
-#ifndef KA_GB_B1
-#define KA_GB_B1 4
-#endif
-  constexpr int B1 = KA_GB_B1;       // barrier #1's group: 4 = right after the F1 read window; 5 / 6
-                                     // give the window's last reads 4 / 8 more MFMAs before lgkmcnt(0)
-  static_assert(B1 >= 4 && B1 <= 6, "barrier #1 group");
-#ifndef KA_GB_DMA_END
-#define KA_GB_DMA_END (KA_GB_DRAIN_B1 ? 24 : 0)
-#endif
+  constexpr int B1 = 4;              // barrier #1's group: right after the F1 read window
+  constexpr int DMA_END = 24;
   // the DMA window: groups B1 .. DE - 1.  The drain at the next call's barrier #1 waits for the window's
   // last piece, so a shorter window leaves it more time to land; but the 64 KB a k-tile stages per CU
   // need about half the k-tile's MFMA time at the L1 fill rate, and windows of 12 groups stalled the
   // MFMA stream (measured, profiles/r5/gemm_big_clamp/README.md: 12 / 16 lose 3-10 %, 20-28 are within
   // 2 % of each other, 24 the best on the gate_up + SwiGLU shape).
-  constexpr int DE = KA_GB_DMA_END > 0 && KA_GB_DMA_END < RW ? KA_GB_DMA_END : RW;
+  constexpr int DE = DMA_END < RW ? DMA_END : RW;   // TN 6: RW = 20
   static_assert(DE > B1 && DE <= RW, "DMA window");
   static_assert(NRD <= 16, "a read window holds 16 reads");
   // read S of a fragment set in window order 1 (A0 B0 A1 B1 ..., the B's past A(TN-1) last):
@@ -543,8 +496,6 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args a) {
   //   groups 4 .. DE-1: the PIECES pieces of k-tile T into buffer BUF, spread evenly
   //   groups RW .. NG-1: F0(t + 1) <- buffer BUF ^ 1, one read before each MFMA (F0(t) retired at
   //                 group GPS - 1)
-  // (KA_GB_DRAIN_B1 0 restores the rounds 3-4 order for timing: lgkmcnt(0) alone at barrier #1 and a
-  // counted vmcnt(PIECES) + barrier #2 at group RW, unsafe: see wait_vm.)
   // (Every DMA is issued unconditionally: skipping the last unit's re-stage behind a runtime flag put
   // VALU work (the flag's mask) into the MFMA stream, where hipcc's register reuse wrote an A-fragment
   // VGPR still being read by an in-flight asm MFMA it cannot see (sparse wrong outputs in the SwiGLU
@@ -574,10 +525,8 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args a) {
           else mfma_acc(acc[q >> 3][q & 7], fa1[q >> 3], fb1[q & 7]);
         });
       }
-      if constexpr (g == 4 && B1 > 4) wait_lgkm<15>();   // row 2 (A2) of F0: all but 15 reads done
       if constexpr (g == B1) {
-        if constexpr (KA_GB_DRAIN_B1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        else wait_lgkm0();
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         block_sync();
       }
       if constexpr (g >= B1 && g < DE) {   // the DMA pieces whose slot falls in this group
@@ -585,10 +534,6 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args a) {
           constexpr int pp = decltype(pc)::value;
           if constexpr (B1 + (pp * (DE - B1)) / PIECES == g) dma(pc, bufc, T);
         });
-      }
-      if constexpr (g == RW && !KA_GB_DRAIN_B1) {
-        wait_vm<PIECES>();
-        block_sync();
       }
       if constexpr (g >= 4 && g < RW) {
         if constexpr (g < GPS) mma4(std::integral_constant<int, g>{}, fa0, fb0);
@@ -625,11 +570,11 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args a) {
     const int nk = nku;
     const int m0 = GR ? gr0 : tm * BM;
     const int mend = GR ? gr0 + gnr : a.M;   // rows past it are not stored
-    // k-tile 0 landed: the PIECES youngest vector-memory operations are k-tile 1's DMA or the previous
-    // tile's epilogue stores, everything older (k-tile 0) is done.  (The previous tile's last call
-    // already read these fragments; reading them again here keeps F0 dead across the epilogue,
+    // k-tiles 0 and 1 landed, and the previous tile's epilogue stores are done (a drain: k-tile 1's
+    // younger pieces may not stay in flight across a wait for k-tile 0's).  (The previous tile's last
+    // call already read these fragments; reading them again here keeps F0 dead across the epilogue,
     // which would otherwise spill.)
-    wait_vm<KA_GB_DRAIN_B1 ? 0 : PIECES>();
+    wait_vm<0>();
     block_sync();
     static_for<NRD>([&](auto sc) { rd2(sc, fa0, fb0, bA00, bB00); });
 #pragma unroll

@@ -15,7 +15,7 @@
 //     applied to the per-lane GLOBAL source address and to the ds_read_b128 address (rule 21), and
 //     makes the 16 rows a ds_read_b128 lane group touches land on 16 distinct 16-B bank slots;
 //   * an LDS ring with stage t + 2 in flight while stage t is computed, waited for with vmcnt(0)
-//     only (KA_GM_SCHED below: LDS-DMA completion is unordered, so a wave never waits while a
+//     only (the two wave sets below: LDS-DMA completion is unordered, so a wave never waits while a
 //     younger stage of its own is in flight); the barrier after the wait publishes every wave's DMA
 //     of the stage and retires the reads of the slot about to be refilled; then ds_read + MFMA;
 //   * XCD-aware tile order (T1): consecutive logical tiles share an XCD (bijective remap of the
@@ -36,35 +36,20 @@ namespace gm {
 
 constexpr int BK = 64;
 
-// diagnostic builds only (tools/gemm_bench, wrong results on purpose): leave out the weight DMA (1),
-// the activation DMA (2), the MFMAs (4) or the fragment reads (8), to find what bounds a shape
-#ifndef KA_GM_ABL
-#define KA_GM_ABL 0
-#endif
-
-
 enum Epi : int { EPI_BF16 = 0, EPI_P32 = 1, EPI_P16 = 2, EPI_SWIGLU = 3 };
 
-// LDS-DMA wait schedule of the ring kernel (KA_GM_SCHED).  LDS-DMA pieces of one wave do NOT always
-// complete in issue order (profiles/r5/gemm_big_clamp/: a younger piece that hits in L2 can retire
-// before an older one), so a counted `s_waitcnt vmcnt(N)` with N > 0 does not prove that the oldest
-// pieces have landed.  The only wait that does is vmcnt(0), so the default schedules are built so that
-// whenever a wave waits for a stage, that stage is the ONLY one it has in flight:
-//   1 (set):  the waves form two sets (w < NW/2, w >= NW/2: one wave of each set per SIMD when
-//             NW = 8); stage t is issued whole by set t & 1, three slots.  At step t set t & 1 holds
-//             only stage t (its next stage, t + 2, is issued after the barrier) and waits vmcnt(0);
-//             the other set holds only stage t + 1 and does not wait.  Same lookahead (stage t + 2
-//             issued at step t) and the same DMA pieces per SIMD per step as the counted ring.
-//   2 (pair): four slots, stages issued in pairs: at even steps every wave drains (vmcnt(0): stages
-//             t, t + 1), one barrier, then issues t + 2, t + 3; odd steps have no wait and no barrier
-//             (the even barrier already published stage t + 1 and every wave finished reading the
-//             slots refilled there).  Configurations whose four slots do not fit LDS use `set`.
-//   0 (counted, rounds 2-5): STAGES slots, vmcnt(PER (STAGES - 2)) + a barrier every step — correct
-//             only under in-order completion; kept for A/B measurements (tools/gemm_bench).
-#ifndef KA_GM_SCHED
-#define KA_GM_SCHED 1
-#endif
+// LDS-DMA wait schedule of the ring kernel.  LDS-DMA pieces of one wave do NOT always complete in
+// issue order (profiles/r5/gemm_big_clamp/: a younger piece that hits in L2 can retire before an
+// older one), so a counted `s_waitcnt vmcnt(N)` with N > 0 does not prove that the oldest pieces have
+// landed.  The only wait that does is vmcnt(0), so whenever a wave waits for a stage, that stage is
+// the ONLY one it has in flight: the waves form two sets (w < NW/2, w >= NW/2: one wave of each set
+// per SIMD when NW = 8); stage t is issued whole by set t & 1, three slots.  At step t set t & 1 holds
+// only stage t (its next stage, t + 2, is issued after the barrier) and waits vmcnt(0); the other set
+// holds only stage t + 1 and does not wait.  Same lookahead (stage t + 2 issued at step t) and the
+// same DMA pieces per SIMD per step as the counted ring of rounds 2-5, which this replaced.
 
+// STAGES_ no longer affects the kernel (the two wave sets always use three slots); it stays because
+// it is part of the kernels' mangled names, so ids 4 and 12 are the same code under two names.
 template <int BN_, int BM_, int WN_, int WM_, int STAGES_, int BK_ = 64>
 struct Cfg {
   static constexpr int BN = BN_, BM = BM_, WN = WN_, WM = WM_, KT = BK_;
@@ -73,16 +58,15 @@ struct Cfg {
   static constexpr int RB = KT * 2;                                  // bytes per staged row
   static constexpr int A_BYTES = BN * RB, B_BYTES = BM * RB;         // one k-step of W / of X
   static constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
-  static constexpr int SCHED = KA_GM_SCHED == 2 ? (4 * STAGE_BYTES <= 160 * 1024 ? 2 : 1) : KA_GM_SCHED;
-  static constexpr int STAGES = SCHED == 1 ? 3 : SCHED == 2 ? 4 : STAGES_;
+  static constexpr int STAGES = 3;
   static constexpr int LDS = STAGES * STAGE_BYTES;
-  // waves that issue one stage's pieces (set: half of them) and each one's DMAs per k-step
-  static constexpr int NI = SCHED == 1 ? NW / 2 : NW;
+  // waves that issue one stage's pieces (one set: half of them) and each one's DMAs per k-step
+  static constexpr int NI = NW / 2;
   static constexpr int GA = A_BYTES / (NI * 64 * 16), GB = B_BYTES / (NI * 64 * 16);
   static_assert(KT == 64 || KT == 32, "k-step is 64 (128-B rows) or 32 (64-B rows)");
   static_assert(TN * WN * 16 == BN && TM * WM * 16 == BM, "tile / wave layout mismatch");
   static_assert(GA * NI * 64 * 16 == A_BYTES && GB * NI * 64 * 16 == B_BYTES, "tile rows must fill whole DMA waves");
-  static_assert(SCHED != 1 || NW % 2 == 0, "set schedule: an even wave count");
+  static_assert(NW % 2 == 0, "two wave sets: an even wave count");
   static_assert(LDS <= 160 * 1024, "LDS budget");
 };
 
@@ -106,18 +90,6 @@ KA_DEV void glds16(const void* g, void* l) {
 template <int N>
 KA_DEV void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// wait until at most `ahead` stages of PER DMAs each are in flight (ahead <= N, static counts)
-template <int N, int PER>
-KA_DEV void wait_ahead(int ahead) {
-  static_assert(N * PER <= 63, "vmcnt immediate");
-  if constexpr (N == 0) {
-    wait_vm<0>();
-  } else {
-    if (ahead >= N) wait_vm<N * PER>();
-    else wait_ahead<N - 1, PER>(ahead);
-  }
 }
 
 KA_DEV void block_sync() {
@@ -240,11 +212,11 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(Args a) {
   const int nk = min(a.kps, a.K - kb) / C::KT;
 
   // per-lane DMA source offsets (bytes, 32-bit): wave-instruction j covers 1 KB = RPI staged rows.
-  // Piece p = j * NI + wi of a stage is issued by issuer wi (set schedule: the wave's index in its set)
+  // Piece p = j * NI + wi of a stage is issued by issuer wi (the wave's index in its set)
   constexpr int CPR = C::RB / 16, RPI = 64 / CPR;   // 16-B chunks per row, rows per instruction
   const int rl = lane / CPR, slot = lane % CPR;
-  const int wi = C::SCHED == 1 ? wave % C::NI : wave;
-  const int wset = C::SCHED == 1 ? wave / C::NI : 0;   // set schedule: this wave issues the stages t, t & 1 == wset
+  const int wi = wave % C::NI;
+  const int wset = wave / C::NI;   // this wave issues the stages t, t & 1 == wset
   uint32_t offA[C::GA], offB[C::GB];
 #pragma unroll
   for (int j = 0; j < C::GA; ++j) {
@@ -272,9 +244,9 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(Args a) {
   const char* Wb = reinterpret_cast<const char*>(Wg);
   const char* Xb = reinterpret_cast<const char*>(a.X);
 
-  // every kernel argument the k-loop needs is read into registers here, before the loop: under
-  // KA_GM_PIPE 2 the asm fragment reads are waited for with a counted lgkmcnt, which a scalar
-  // (s_load) kernarg read issued between the reads and that wait would break.  The asm makes wnt an
+  // every kernel argument the k-loop needs is read into registers here, before the loop: the asm
+  // fragment reads are waited for with a counted lgkmcnt, which a scalar (s_load) kernarg read
+  // issued between the reads and that wait would break.  The asm makes wnt an
   // opaque SGPR value, so hipcc cannot rematerialise it from the kernarg segment inside the loop
   // (build.py check_lgkm_windows verifies the k-loop's read windows in the generated assembly).
   int wnt = a.wnt;
@@ -287,27 +259,23 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(Args a) {
     char* sb = sa + C::A_BYTES;
     const uint32_t kofs = (uint32_t)t * C::RB;
     const int lo = part == 1 ? HALF_P : 0, hi = part == 0 ? HALF_P : NPC;
-    if (!(KA_GM_ABL & 1)) {
-      if (wnt) {
+    if (wnt) {
 #pragma unroll
-        for (int j = 0; j < C::GA; ++j)
-          if (j >= lo && j < hi) glds16<2>(Wb + offA[j] + kofs, sa + (j * C::NI + wi) * 1024);
-      } else {
+      for (int j = 0; j < C::GA; ++j)
+        if (j >= lo && j < hi) glds16<2>(Wb + offA[j] + kofs, sa + (j * C::NI + wi) * 1024);
+    } else {
 #pragma unroll
-        for (int j = 0; j < C::GA; ++j)
-          if (j >= lo && j < hi) glds16(Wb + offA[j] + kofs, sa + (j * C::NI + wi) * 1024);
-      }
+      for (int j = 0; j < C::GA; ++j)
+        if (j >= lo && j < hi) glds16(Wb + offA[j] + kofs, sa + (j * C::NI + wi) * 1024);
     }
-    if (!(KA_GM_ABL & 2)) {
 #pragma unroll
-      for (int j = 0; j < C::GB; ++j)
-        if (C::GA + j >= lo && C::GA + j < hi) glds16(Xb + offB[j] + kofs, sb + (j * C::NI + wi) * 1024);
-    }
+    for (int j = 0; j < C::GB; ++j)
+      if (C::GA + j >= lo && C::GA + j < hi) glds16(Xb + offB[j] + kofs, sb + (j * C::NI + wi) * 1024);
   };
-  // stage t's pieces, issued by the waves that own it (every wave, or set t & 1)
+  // stage t's pieces, issued by the waves of the set that owns it (set t & 1)
   auto issue_own = [&](int t, int part = -1) {
     if (t >= nk) return;
-    if (C::SCHED == 1 && (t & 1) != wset) return;
+    if ((t & 1) != wset) return;
     issue(t % C::STAGES, t, part);
   };
 
@@ -328,21 +296,16 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(Args a) {
   // finished reading before the barrier), then the MFMAs: one LDS round trip per k-step is exposed,
   // overlapped with the DMA issue, instead of one per k-half with the DMA issue in front (with one
   // wave per SIMD nothing else hides it): 2-7 % on the decode plan's shapes (profiles/r4/gm_pipe/).
-  // KA_GM_PIPE 2 (default): the reads are asm and each k-half's MFMAs wait with a counted lgkmcnt
-  // for their own fragments only (hipcc's own bookkeeping emits lgkmcnt(0) before the first MFMA):
-  // 0-10 % more.  1: the same order with compiler-issued reads and waits.  A branch-free variant (tail
-  // DMAs clamped, one constant vmcnt) measured no better and lost 7 % on 8-step k-loops.
-#ifndef KA_GM_PIPE
-#define KA_GM_PIPE 2
-#endif
+  // The reads are asm and each k-half's MFMAs wait with a counted lgkmcnt for their own fragments
+  // only (hipcc's own bookkeeping emits lgkmcnt(0) before the first MFMA): 0-10 % more than the same
+  // order with compiler-issued reads and waits.  A branch-free variant (tail DMAs clamped, one
+  // constant vmcnt) measured no better and lost 7 % on 8-step k-loops.
   bf16x8 fa[C::KT / 32][C::TN], fb[C::KT / 32][C::TM];
-#if KA_GM_PIPE == 2
   // asm fragment reads, in the order fa[0][..], fb[0][..], fa[1][..], ...: k-half kk's MFMAs wait with
   // lgkmcnt((KT / 32 - 1 - kk) (TN + TM)) for their own fragments only (LDS-DMA counts on vmcnt alone)
   static_assert(C::TN + C::TM <= 15, "lgkmcnt immediate");
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) u32x4*)lds;
   auto read_frags_asm = [&](int stage) {
-    if (KA_GM_ABL & 8) return;
     const uint32_t base = lds0 + (uint32_t)(stage * C::STAGE_BYTES);
 #pragma unroll
     for (int kk = 0; kk < C::KT / 32; ++kk) {
@@ -364,41 +327,18 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(Args a) {
 #pragma unroll
     for (int j = 0; j < C::TM; ++j) asm volatile("" : "+v"(fb[kk][j]));
   };
-#endif
-  auto read_frags = [&](int stage) {
-    const char* sa = lds_c + stage * C::STAGE_BYTES;
-    const char* sb = sa + C::A_BYTES;
-#pragma unroll
-    for (int kk = 0; kk < C::KT / 32; ++kk) {
-      const int ch = kk ? ch1 : ch0;
-#pragma unroll
-      for (int i = 0; i < C::TN; ++i)
-        fa[kk][i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(sa + rdA + i * 16 * C::RB + ch));
-#pragma unroll
-      for (int j = 0; j < C::TM; ++j)
-        fb[kk][j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(sb + rdB + j * 16 * C::RB + ch));
-    }
-  };
   auto mma_half = [&](int kk) {
-    if (KA_GM_ABL & 4) return;
 #pragma unroll
     for (int i = 0; i < C::TN; ++i)
 #pragma unroll
       for (int j = 0; j < C::TM; ++j)
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk][i], fb[kk][j], acc[i][j], 0, 0, 0);
   };
-  auto mma = [&]() {
-#pragma unroll
-    for (int kk = 0; kk < C::KT / 32; ++kk) mma_half(kk);
-  };
 
-  // prologue: STAGES - 1 stages in flight (set / pair schedules: stages 0 and 1)
+  // prologue: stages 0 and 1 in flight, one per set
 #pragma unroll
-  for (int s = 0; s < (C::SCHED == 0 ? C::STAGES - 1 : 2); ++s) issue_own(s);
-  constexpr int PER = C::GA + C::GB;
-#if KA_GM_PIPE == 2
+  for (int s = 0; s < 2; ++s) issue_own(s);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // no scalar load left in flight: lgkm counts in order
-#endif
 #ifdef GM_KSTAMP
   unsigned long long ks[4] = {0, 0, 0, 0}, kt_e = __builtin_amdgcn_s_memtime();
 #endif
@@ -407,55 +347,25 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(Args a) {
     const unsigned long long kt_a = __builtin_amdgcn_s_memtime();
     ks[3] += kt_a - kt_e;
 #endif
-    // stage t landed (this wave's part), then the barrier publishes every wave's part
-    if constexpr (C::SCHED == 1) {
-      if ((t & 1) == wset) wait_vm<0>();   // stage t is this set's only stage in flight
-      block_sync();
-    } else if constexpr (C::SCHED == 2) {
-      if (!(t & 1)) {                      // stages t, t + 1: this wave's only pieces in flight
-        wait_vm<0>();
-        block_sync();
-      }
-    } else if constexpr (C::STAGES >= 3) {
-      // counted: stages t+1 .. min(nk-1, t+STAGES-2) of this wave stay in flight
-      wait_ahead<C::STAGES - 2, PER>(min(nk - 1 - t, C::STAGES - 2));
-      block_sync();
-    } else {
-      wait_vm<0>();
-      block_sync();
-    }
+    // stage t landed (its set's part), then the barrier publishes every wave's part
+    if ((t & 1) == wset) wait_vm<0>();   // stage t is this set's only stage in flight
+    block_sync();
 #ifdef GM_KSTAMP
     const unsigned long long kt_b = __builtin_amdgcn_s_memtime();
     ks[0] += kt_b - kt_a;
 #endif
     if (t == 0) BSTAMP(1);
-    // refill: the slot(s) every wave finished reading before the last barrier.  KA_GM_SPLIT_ISSUE: the
-    // set / pair schedules issue twice a wave's usual pieces at once, so half of them go after the
-    // first k-half's MFMAs (issued while the matrix pipe works) instead of all ahead of them
-    auto refill = [&](int part) {
-      if constexpr (C::SCHED == 2) {
-        if (!(t & 1)) {
-          if (part != 1) issue_own(t + 2);
-          if (part != 0) issue_own(t + 3);
-        }
-      } else {
-        issue_own(t + C::STAGES - 1, part);
-      }
-    };
-#ifndef KA_GM_SPLIT_ISSUE
-#define KA_GM_SPLIT_ISSUE 1
-#endif
-    constexpr bool split_issue = KA_GM_SPLIT_ISSUE && C::SCHED != 0 && C::KT == 64;
-#if KA_GM_PIPE == 2
+    // refill: the slot every wave finished reading before the last barrier.  A set issues twice a
+    // wave's usual pieces at once, so with two k-halves half of them go after the first k-half's MFMAs
+    // (issued while the matrix pipe works) instead of all ahead of them
+    auto refill = [&](int part) { issue_own(t + C::STAGES - 1, part); };
     read_frags_asm(t % C::STAGES);
-    refill(split_issue ? 0 : -1);
+    refill(C::KT == 64 ? 0 : -1);
     wait_frags(0);
     mma_half(0);
     if constexpr (C::KT == 64) {
-      if constexpr (split_issue) {
-        __builtin_amdgcn_sched_barrier(0);
-        refill(1);
-      }
+      __builtin_amdgcn_sched_barrier(0);
+      refill(1);
       __builtin_amdgcn_sched_barrier(0);   // the first k-half's MFMAs stay above the second wait
       wait_frags(1);
 #ifdef GM_KSTAMP
@@ -468,13 +378,6 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(Args a) {
       ks[2] += kt_e - kt_d;
 #endif
     }
-#else
-    read_frags(t % C::STAGES);
-    __builtin_amdgcn_sched_barrier(0);
-    refill(-1);
-    __builtin_amdgcn_sched_barrier(0);
-    mma();
-#endif
   }
   BSTAMP(2);
 #ifdef GM_KSTAMP
@@ -549,8 +452,7 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(Args a) {
 // Eight waves in two groups of four, one wave of each group per SIMD.  Group g computes W rows
 // [128g, 128g + 128) of the tile (its A half-tile is private to it) against X rows [64c, 64c + 64)
 // (c = wave & 3).  Group 1 runs one barrier behind group 0, so on every SIMD one wave issues MFMAs
-// while its partner reads LDS / issues DMAs (T3/T4 structure, counted vmcnt, raw s_barrier, setprio
-// T5).  LDS: 2 buffers x {A0, A1, B0, B1} half-tiles of 128 rows x 128 B (16 KB), XOR-swizzled.
+// while its partner reads LDS / issues DMAs (T3/T4 structure, raw s_barrier, setprio T5).  LDS: 2 buffers x {A0, A1, B0, B1} half-tiles of 128 rows x 128 B (16 KB), XOR-swizzled.
 // WAR: a half-tile is refilled only after the last reader group passed the barrier following the
 // C phase that consumed its reads (the analysis is in docs/ARCHITECTURE.md).  A 4-phase variant
 // (16 MFMAs per phase) measured slower than this 2-phase one (profiles/r2/gemm_pp_phase_stamps.txt:
@@ -563,24 +465,17 @@ struct PP {
 // Two phases per k-tile (32 MFMAs per C phase: the barrier bubble measured by the s_memtime
 // stamps, ~120 cycles per barrier interval, is paid half as often).  Phase a: n-half 0 against
 // all of the wave's B columns (R_a: A-sub0 + B = 16 reads), phase b: n-half 1 (R_b: A-sub1).
-// DMA schedule (group 0 | group 1), tile t+2 into buffer t & 1:
-//   B0 B1 (t+2):  G0 in R_a(t+1) | G1 in R_b(t)       (B of tile t last read by G1's R_a(t))
-//   A0 A1 (t+2):  G0 in R_b(t+1) | G1 in R_a(t+1)     (A_g of tile t last read by group g's R_b(t))
-// Waits before the barrier that ends interval 4t+7: G0 (end of C_b(t+1)) vmcnt(0), G1 (end of its
-// R_b(t+1), which issued B(t+3)) vmcnt(4).
-// KA_PP_SAFE 1: the counted vmcnt(4) of G1 is only correct under in-order LDS-DMA completion
-// (see KA_GM_SCHED), so group 0 issues every piece instead: B(t+1) in its R_a(t), A(t+1) in its R_b(t)
-// (4 pieces per wave and half-tile), and drains vmcnt(0) at the end of C_b(t) — its only pieces in
-// flight are tile t+1's — before the barrier ahead of the first read of tile t+1; group 1 never waits.
-// WAR: B(t+1) overwrites B(t-1), last read by G1's R_a(t-1) three intervals earlier; A(t+1) overwrites
-// A(t-1), last read by G1's R_b(t-1), retired before G1's C_b(t-1), one interval before G0's R_b(t).
-// KA_PP_SAFE 2 (default): both groups issue, each drains with nothing younger in flight: G0 as above
-// with its half of the pieces (B(t+1) in R_a(t), A(t+1) in R_b(t), vmcnt(0) at the end of C_b(t)); G1
-// issues its halves of A(t+1) AND B(t+1) in its R_a(t) and drains vmcnt(0) at the end of its R_b(t),
-// the barrier before G0's R_a(t+1).  WAR for G1's B(t+1): B(t-1) was last read by G1's R_a(t-1).
-#ifndef KA_PP_SAFE
-#define KA_PP_SAFE 2
-#endif
+// DMA schedule, tile t+1 into buffer (t+1) & 1; every wave issues 2 pieces of each half-tile, and each
+// group drains with nothing younger in flight (LDS-DMA completion is unordered: see the ring kernel):
+//   G0: its half of B(t+1) in R_a(t), of A(t+1) in R_b(t); vmcnt(0) at the end of C_b(t) — its only
+//       pieces in flight are tile t+1's — before the barrier ahead of the first read of tile t+1;
+//   G1: its halves of A(t+1) AND B(t+1) in its R_a(t); vmcnt(0) at the end of its R_b(t), the barrier
+//       before G0's R_a(t+1).
+// WAR: B(t+1) overwrites B(t-1), last read by G1's R_a(t-1); A(t+1) overwrites A(t-1), last read by
+// G1's R_b(t-1), retired before G1's C_b(t-1), one interval before G0's R_b(t).
+// The schedule of rounds 2-5 kept B(t+2) in flight behind a counted vmcnt(4) in group 1, correct only
+// under in-order completion; a drained variant in which group 0 issued every piece measured the same
+// within noise (profiles/r6/lds_dma_safety/pp2_variants_time_r6c.log).  Both are gone.
 template <int EPI, bool GROUPED = false>
 __global__ __launch_bounds__(512) void gemm_pp2_kernel(Args a) {
   extern __shared__ __attribute__((aligned(16))) u32x4 lds[];
@@ -603,13 +498,12 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(Args a) {
   const int nk = min(a.kps, a.K - kb) / BK;
 
   const int r8 = lane >> 3, slot = lane & 7;
-  // pieces of a half-tile issued per wave (KA_PP_SAFE: group 0 issues all 16), and the wave's index
-  constexpr int PJ = KA_PP_SAFE == 1 ? 4 : 2, PW = KA_PP_SAFE == 1 ? 4 : 8;
-  const int wq = KA_PP_SAFE == 1 ? wc : w;
+  // pieces of a half-tile (16) issued per wave, and the waves that share them
+  constexpr int PJ = 2, PW = 8;
   uint32_t off[4][PJ];
 #pragma unroll
   for (int j = 0; j < PJ; ++j) {
-    const int row = (j * PW + wq) * 8 + r8;
+    const int row = (j * PW + w) * 8 + r8;
     const uint32_t ch = (uint32_t)(slot ^ ((row >> 1) & 7)) * 8;
     off[0][j] = ((uint32_t)wrap_row(n0 + row, a.N) * (uint32_t)a.K + kb + ch) * 2u;
     off[1][j] = ((uint32_t)wrap_row(n0 + 128 + row, a.N) * (uint32_t)a.K + kb + ch) * 2u;
@@ -633,10 +527,10 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(Args a) {
     const uint32_t kofs = (uint32_t)t * (BK * 2);
     if (h < 2 && a.wnt) {
 #pragma unroll
-      for (int j = 0; j < PJ; ++j) glds16<2>(src + off[h][j] + kofs, dst + (j * PW + wq) * 1024);
+      for (int j = 0; j < PJ; ++j) glds16<2>(src + off[h][j] + kofs, dst + (j * PW + w) * 1024);
     } else {
 #pragma unroll
-      for (int j = 0; j < PJ; ++j) glds16(src + off[h][j] + kofs, dst + (j * PW + wq) * 1024);
+      for (int j = 0; j < PJ; ++j) glds16(src + off[h][j] + kofs, dst + (j * PW + w) * 1024);
     }
   };
 
@@ -679,7 +573,6 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(Args a) {
     __builtin_amdgcn_s_setprio(0);
   };
 
-#if KA_PP_SAFE == 2
   // prologue: tile 0 (every wave its pieces), drained; then tile 1, drained by each group at its point
   for (int h = 0; h < 4; ++h) issue(h, 0);
   wait_vm<0>();
@@ -707,64 +600,6 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(Args a) {
     block_sync();
   }
   if (g == 0) block_sync();
-#elif KA_PP_SAFE == 1
-  // prologue: group 0 issues tile 0, drains it, issues tile 1 (drained at the end of C_b(0))
-  if (g == 0) {
-    for (int h = 0; h < 4; ++h) issue(h, 0);
-    wait_vm<0>();
-    for (int h = 0; h < 4; ++h) issue(h, 1);
-  }
-  block_sync();
-  if (g == 1) block_sync();
-
-  for (int t = 0; t < nk; ++t) {
-    const char* buf = L + (t & 1) * PP::BUF;
-    const int t1 = t == 0 ? nk : t + 1;   // tile 1 was issued whole by the prologue
-    // phase a
-    read_a(buf, 0); read_b(buf);
-    if (g == 0) { issue(2, t1); issue(3, t1); }   // B(t+1): G0 in R_a(t)
-    block_sync();
-    mma(0);
-    block_sync();
-    // phase b
-    read_a(buf, 1);
-    if (g == 0) { issue(0, t1); issue(1, t1); }   // A(t+1): G0 in R_b(t)
-    block_sync();
-    mma(1);
-    if (g == 0) wait_vm<0>();                     // tile t+1: G0's only pieces in flight
-    block_sync();
-  }
-  if (g == 0) block_sync();
-#else
-  // prologue: tiles 0 and 1 (all four half-tiles each); wait for tile 0; group 1 one barrier behind
-  for (int h = 0; h < 4; ++h) issue(h, 0);
-  for (int h = 0; h < 4; ++h) issue(h, 1);
-  if (nk > 1) wait_vm<8>(); else wait_vm<0>();
-  block_sync();
-  if (g == 1) block_sync();
-
-  for (int t = 0; t < nk; ++t) {
-    const char* buf = L + (t & 1) * PP::BUF;
-    const int t1 = t == 0 ? nk : t + 1;   // tile 1 was issued whole by the prologue
-    // phase a
-    read_a(buf, 0); read_b(buf);
-    if (g == 0) { issue(2, t1); issue(3, t1); }   // B(t+1): G0 in R_a(t)
-    else { issue(0, t1); issue(1, t1); }          // A(t+1): G1 in R_a(t)
-    block_sync();
-    mma(0);
-    block_sync();
-    // phase b
-    read_a(buf, 1);
-    if (g == 0) { issue(0, t1); issue(1, t1); }   // A(t+1): G0 in R_b(t)
-    else { issue(2, t + 2); issue(3, t + 2); }    // B(t+2): G1 in R_b(t)
-    if (g == 1) { if (t + 2 < nk) wait_vm<4>(); else wait_vm<0>(); }
-    block_sync();
-    mma(1);
-    if (g == 0) wait_vm<0>();
-    block_sync();
-  }
-  if (g == 0) block_sync();
-#endif
 
   const int nb = n0 + 128 * g + 4 * grp;
   const int mb = m0 + 64 * wc + r16;
@@ -867,12 +702,12 @@ static int launch_grouped(const Args& a0, int split, hipStream_t st) {
 }
 
 // ---- configurations ------------------------------------------------------------------------------
-// id: BN x BM tile, WN x WM waves (per-wave tile), ring stages of BK = 64:
-//   2: 128 x 256, 2 x 4 waves (64 x 64), 3 stages                (8 waves, 144 KB: 1 block/CU)
-//   3: 256 x 128, 4 x 2 waves ( 64 x 64), 3 stages
-//   4: 128 x 128, 2 x 2 waves ( 64 x 64), 3 stages                (4 waves, 96 KB: 1 block/CU)
-//   5: 128 x  64, 2 x 1 waves ( 64 x 64), 3 stages                (decode M <= 64)
-//  12: 128 x 128 with 4 stages
+// id: BN x BM tile, WN x WM waves (per-wave tile), three ring stages of BK = 64:
+//   2: 128 x 256, 2 x 4 waves (64 x 64)                           (8 waves, 144 KB: 1 block/CU)
+//   3: 256 x 128, 4 x 2 waves ( 64 x 64)
+//   4: 128 x 128, 2 x 2 waves ( 64 x 64)                          (4 waves, 96 KB: 1 block/CU)
+//   5: 128 x  64, 2 x 1 waves ( 64 x 64)                          (decode M <= 64)
+//  12: as 4 (once its 4-stage ring; the `s` column no longer affects the kernel, see Cfg)
 //  19: 256 x 256 2-phase ping-pong (gemm_pp2_kernel), 8 waves in two staggered groups
 // (ids are stable across rounds: the removed configurations' numbers are not reused)
 #define GM_CFGS(X)               \
@@ -884,13 +719,12 @@ static int launch_grouped(const Args& a0, int split, hipStream_t st) {
   X(6, 96, 256, 2, 2, 3, 64)      \
   X(8, 192, 128, 2, 2, 3, 64)     \
   GM_EXTRA_CFGS(X)
-// measurement-only configurations (tools/gemm_bench -DKA_GM_EXTRA): 32-deep k-steps, deeper rings
+// measurement-only configurations (tools/gemm_bench -DKA_GM_EXTRA): 32-deep k-steps
 #ifdef KA_GM_EXTRA
 #define GM_EXTRA_CFGS(X)          \
   X(20, 128, 256, 2, 4, 6, 32)    \
   X(21, 128, 128, 2, 2, 8, 32)    \
-  X(22, 256, 128, 4, 2, 6, 32)    \
-  X(23, 128, 256, 2, 4, 5, 32)
+  X(22, 256, 128, 4, 2, 6, 32)
 #else
 #define GM_EXTRA_CFGS(X)
 #endif

@@ -870,7 +870,7 @@ def test_gemm_big_linear_split_tail_vs_fp32(M, N, K):
     w = (torch.randn(N, K, device=DEV) / math.sqrt(K)).to(BF)
     want = x.float() @ w.float().t()
     for _ in range(4):   # later launches run on counters the first one reset; a stale-slab read
-        # (the plain-load hand-off, KA_GB_TAIL_MODE 0 / 1) showed in some launches only
+        # (the retired plain-load hand-offs behind fences) showed in some launches only
         got = ops.linear_big(x, w)
         close(got, want, atol=3e-2, rtol=2e-2)
     ws = ops.gemm_big_ws(torch.device(DEV))
@@ -924,7 +924,7 @@ def test_gm_dispatched_plans_alternating_launches_exact(amplify):
     persisted decode plan dispatches for Llama-3-8B buckets 128-512 (bf16 split-K partials included),
     each launch right after an unrelated GEMM and checked whole against fp32 — with the duplicate-address
     amplifier (ldx = 0: every X piece reads 8 identical rows) and without.  The kernels wait for LDS-DMA
-    with vmcnt(0) only (KA_GM_SCHED / KA_PP_SAFE), so no launch may be wrong; >= 500 launches per
+    with vmcnt(0) only (the ring's two wave sets, the ping-pong's drained groups), so no launch may be wrong; >= 500 launches per
     combination: scripts/gm_plan_stress.py, profiles/r6/lds_dma_safety/."""
     from ai_agent_kubectl_amd.ops import stress
     combos = stress.dispatched_combos()

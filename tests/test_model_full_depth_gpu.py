@@ -201,7 +201,7 @@ def test_persistent_decode_repeatable_under_alternating_launches(eng, B):
     KV append is idempotent) launched again and again, each launch right after an unrelated GEMM, must
     give the bitwise-same hidden states: the kernel has one fixed summation order, so a weight piece
     read from its LDS ring before it landed shows as a differing repeat.  The streams wait for their
-    pieces with vmcnt(0) only (KA_PD_SAFE drained halves)."""
+    pieces with vmcnt(0) only (each ring's two drained halves)."""
     be = EngineLLM(eng, max_new_tokens=40, ignore_eos=True)
     params = SamplingParams(max_new_tokens=40, ignore_eos=True)
     sch, r, m = eng.scheduler, eng.runner, eng.runner.model

@@ -97,7 +97,7 @@ def test_plan_for_takes_the_next_bucket_up():
 
 def test_lgkm_window_checker_flags_compiler_lgkm_ops():
     """build.py re-verifies that no compiler-issued LGKM operation sits between the
-    k-loop's asm fragment reads and their counted lgkmcnt wait (gemm_mfma KA_GM_PIPE 2, gemm_big)."""
+    k-loop's asm fragment reads and their counted lgkmcnt wait (gemm_mfma's ring kernel, gemm_big)."""
     from ai_agent_kubectl_amd.build import lgkm_window_violations
     ok = """_ZN2gm11gemm_kernelI1EEvNS_4ArgsE:
 \t;;#ASMSTART
@@ -116,6 +116,26 @@ def test_lgkm_window_checker_flags_compiler_lgkm_ops():
     n, bad = lgkm_window_violations(broken, "gemm_kernel")
     assert n == 1 and len(bad) == 1 and "s_load_dwordx2" in bad[0][2]
     assert lgkm_window_violations(broken, "other_kernel") == (0, [])
+
+
+def test_retired_schedule_macros_stay_out_of_csrc():
+    """The counted-vmcnt LDS-DMA waits, the row clamp, the fenced tail hand-offs and the k-loop ablations
+    were compile-time variants of the three hot kernels until they were deleted (the table in
+    docs/PERFORMANCE_HISTORY.md).  No source may bring one back behind its old switch."""
+    import glob
+    import os
+    from ai_agent_kubectl_amd.build import CSRC
+    retired = ("KA_PD_SAFE", "KA_PD_PREISSUE", "KA_PD_NT", "KA_PD_ROT", "KA_PD_RING", "KA_GM_ABL", "KA_GM_SCHED",
+               "KA_GM_PIPE", "KA_GM_SPLIT_ISSUE", "KA_PP_SAFE", "KA_GB_CLAMP", "KA_GB_DRAIN_B1", "KA_GB_TAIL_MODE",
+               "KA_GB_B1", "KA_GB_DMA_END")
+    srcs = sorted(glob.glob(os.path.join(CSRC, "*.h*")))   # *.hip and *.h
+    assert len(srcs) >= 10, srcs
+    found = []
+    for path in srcs:
+        with open(path, errors="replace") as f:
+            text = f.read()
+        found += [(os.path.basename(path), name) for name in retired if name in text]
+    assert found == []
 
 
 def test_plan_ladder_anomalies_flags_slower_smaller_bucket():
