@@ -26,27 +26,7 @@
 #define HD 128
 #define KBS 16
 
-// P re-layout scratch (per wave): the softmax probabilities leave the MFMA C layout (lane (col, grp)
-// holds rows 4 grp + r, keys col and 16 + col) and are re-read in the A layout (lane holds row col,
-// keys 8 grp .. 8 grp + 7).  16 rows x PSTR = 40 bf16 (64 B of P + 16 B of padding); 16-B chunk c of
-// row x sits at slot c ^ p_slot_xor(x >> 2).  Neighbouring lanes swap one probability so that every
-// lane stores one dword (even lanes keys col, col + 1; odd lanes keys 15 + col, 16 + col).  With the
-// 80-B stride and this XOR both the stores (2 x 32 lanes on 32 banks) and the ds_read_b128 reads
-// (4 x 16 lanes on 64 banks, MI355X_MICROARCH.md §LDS) are conflict-free — found by exhaustive search
-// over strides and XOR maps; the previous 64-B rows cost 15-20 % extra LDS cycles.
-constexpr int PSTR = 40;
-KA_DEV int p_slot_xor(int q) { return (q ^ (q >> 1)) & 1; }
-KA_DEV void p_store(bf16_t* pw, int prow, int col, float p0, float p1) {
-  const float q0 = dpp_f<0xB1>(p0), q1 = dpp_f<0xB1>(p1);   // lane ^ 1
-  const bool even = (col & 1) == 0;
-  const int key = even ? col : 15 + col;
-  const uint32_t v = even ? pack2(p0, q0) : pack2(q1, p1);
-  const int slot = (key >> 3) ^ p_slot_xor(prow >> 2);
-  *reinterpret_cast<uint32_t*>(pw + prow * PSTR + (slot << 3) + (key & 7)) = v;
-}
-KA_DEV bf16x8 p_load(const bf16_t* pw, int col, int grp) {
-  return as_bf16x8(*reinterpret_cast<const uint4*>(pw + col * PSTR + ((grp ^ p_slot_xor((col >> 2) & 3)) << 3)));
-}
+// The per-wave P re-layout scratch (PSTR, p_store, p_load) is common.h's.
 
 // ------------------------------------------------------------------------------------------------
 // Fused decode step (FUSED = true): the workgroup of (kv head h, sequence b) first does what
@@ -78,40 +58,14 @@ struct DecodeFuse {
   float* part_ml;     // [B, hq, 2]
 };
 
-// The slices are loaded DQ_UNROLL at a time, each batch issued before its first add (a rolled loop
-// waited for each slice's load before issuing the next: `split` serial memory latencies in the
-// kernel's prologue; the TP = 8 rank's QKV runs split 12).  Summed in order k = 0, 1, ...
+// N reads of 4 consecutive QKV elements as packed bf16 (a thread's q / k rotary halves and its
+// new-value dims): straight from qkv, or summed in fp32 over the `split` split-K slices of P (fp32, or
+// bf16 from gemm_mfma EPI_P16) in order k = 0, 1, ...  The slices are loaded DQ_UNROLL at a time, each
+// batch issued before its first add (a rolled loop waited for each slice's load before issuing the
+// next: `split` serial memory latencies in the kernel's prologue; the TP = 8 rank's QKV runs split 12),
+// and every batch issues the N reads' slices together, so the N reductions cost one round trip per
+// batch, not N.
 constexpr int DQ_UNROLL = 4;
-__device__ __forceinline__ uint2 dq_ld4(const DecodeFuse& f, size_t off) {
-  if (f.P == nullptr) return *reinterpret_cast<const uint2*>(f.qkv + off);
-  f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (f.pbf16) {   // bf16 slices (gemm_mfma EPI_P16): summed in fp32
-    const bf16_t* pb = reinterpret_cast<const bf16_t*>(f.P);
-    for (int k0 = 0; k0 < f.split; k0 += DQ_UNROLL) {
-      uint2 q[DQ_UNROLL];
-#pragma unroll
-      for (int k = 0; k < DQ_UNROLL; ++k)
-        if (k0 + k < f.split) q[k] = *reinterpret_cast<const uint2*>(pb + (k0 + k) * f.pstride + off);
-#pragma unroll
-      for (int k = 0; k < DQ_UNROLL; ++k)
-        if (k0 + k < f.split) s += f32x4{lo_f(q[k].x), hi_f(q[k].x), lo_f(q[k].y), hi_f(q[k].y)};
-    }
-    return make_uint2(pack2(s[0], s[1]), pack2(s[2], s[3]));
-  }
-  for (int k0 = 0; k0 < f.split; k0 += DQ_UNROLL) {
-    f32x4 p[DQ_UNROLL];
-#pragma unroll
-    for (int k = 0; k < DQ_UNROLL; ++k)
-      if (k0 + k < f.split) p[k] = *reinterpret_cast<const f32x4*>(f.P + (k0 + k) * f.pstride + off);
-#pragma unroll
-    for (int k = 0; k < DQ_UNROLL; ++k)
-      if (k0 + k < f.split) s += p[k];
-  }
-  return make_uint2(pack2(s[0], s[1]), pack2(s[2], s[3]));
-}
-
-// N reads of dq_ld4 at once (a thread's q / k rotary halves and its new-value dims): every batch
-// issues the N reads' slices together, so the N reductions cost one round trip per batch, not N.
 template <int N>
 __device__ __forceinline__ void dq_ld4n(const DecodeFuse& f, const size_t (&off)[N], const bool (&en)[N],
                                         uint2 (&out)[N]) {
@@ -467,9 +421,7 @@ static bool decode_two_waves(int batch, int hq, int hkv) {
   static int min_wgs = -1;
   if (min_wgs < 0) {
     const char* e = getenv("KA_DECODE_NW2_MIN_WGS");
-    int cus = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    min_wgs = e ? atoi(e) : 4 * cus;
+    min_wgs = e ? atoi(e) : 4 * ka_num_cus();
   }
   const int G = hq / hkv;
   return min_wgs > 0 && (long)batch * hkv > min_wgs && (G + 1) * HD <= 2 * 16 * PSTR;

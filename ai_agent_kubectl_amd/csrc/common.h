@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <utility>
+
 typedef uint16_t bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -60,17 +62,11 @@ KA_DEV float row16_sum(float v) {
   return v;
 }
 
-// whole-wave reductions: the 16-lane row by DPP, then the four rows by two lane swaps
+// whole-wave reduction: the 16-lane row by DPP, then the four rows by two lane swaps
 KA_DEV float wave_sum(float v) {
   v = row16_sum(v);
   v += __shfl_xor(v, 16, 64);
   v += __shfl_xor(v, 32, 64);
-  return v;
-}
-KA_DEV float wave_max(float v) {
-  v = row16_max(v);
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  v = fmaxf(v, __shfl_xor(v, 32, 64));
   return v;
 }
 
@@ -95,3 +91,90 @@ KA_DEV u32x4 swiglu8(u32x4 g, u32x4 u) {
   }
   return o;
 }
+
+// ---- bf16 dot product -----------------------------------------------------------------------------
+// acc + the dot product of two 16-B words of 8 bf16 each, on v_dot2c_f32_bf16: the row-streaming
+// GEMVs of gemm_skinny.hip and decode_persistent.hip
+KA_DEV float dot8(uint4 w, uint4 x, float acc) {
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, w.x), __builtin_bit_cast(bf16x2_t, x.x), acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, w.y), __builtin_bit_cast(bf16x2_t, x.y), acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, w.z), __builtin_bit_cast(bf16x2_t, x.z), acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, w.w), __builtin_bit_cast(bf16x2_t, x.w), acc, false);
+  return acc;
+}
+
+// ---- P re-layout scratch of the MFMA attention kernels (attention.hip, decode_persistent.hip) ------
+// Per wave: the softmax probabilities leave the MFMA C layout (lane (col, grp) holds rows 4 grp + r,
+// keys col and 16 + col) and are re-read in the A layout (lane holds row col, keys 8 grp .. 8 grp + 7).
+// 16 rows x PSTR = 40 bf16 (64 B of P + 16 B of padding); 16-B chunk c of row x sits at slot
+// c ^ p_slot_xor(x >> 2).  Neighbouring lanes swap one probability so that every lane stores one dword
+// (even lanes keys col, col + 1; odd lanes keys 15 + col, 16 + col).  With the 80-B stride and this XOR
+// both the stores (2 x 32 lanes on 32 banks) and the ds_read_b128 reads (4 x 16 lanes on 64 banks,
+// MI355X_MICROARCH.md §LDS) are conflict-free — found by exhaustive search over strides and XOR maps;
+// the previous 64-B rows cost 15-20 % extra LDS cycles.
+constexpr int PSTR = 40;
+KA_DEV int p_slot_xor(int q) { return (q ^ (q >> 1)) & 1; }
+KA_DEV void p_store(bf16_t* pw, int prow, int col, float p0, float p1) {
+  const float q0 = dpp_f<0xB1>(p0), q1 = dpp_f<0xB1>(p1);   // lane ^ 1
+  const bool even = (col & 1) == 0;
+  const int key = even ? col : 15 + col;
+  const uint32_t v = even ? pack2(p0, q0) : pack2(q1, p1);
+  const int slot = (key >> 3) ^ p_slot_xor(prow >> 2);
+  *reinterpret_cast<uint32_t*>(pw + prow * PSTR + (slot << 3) + (key & 7)) = v;
+}
+KA_DEV bf16x8 p_load(const bf16_t* pw, int col, int grp) {
+  return as_bf16x8(*reinterpret_cast<const uint4*>(pw + col * PSTR + ((grp ^ p_slot_xor((col >> 2) & 3)) << 3)));
+}
+
+// ---- LDS-DMA GEMM kernels (gemm_big.hip, gemm_mfma.hip) ---------------------------------------------
+// compile-time unrolled loop: f(std::integral_constant<int, 0>{}) ... f(..N-1): asm immediates
+// ("i" operands) need constants, which a #pragma-unrolled loop variable is not
+template <class F, int... S>
+KA_DEV void static_for_impl(F&& f, std::integer_sequence<int, S...>) {
+  (f(std::integral_constant<int, S>{}), ...);
+}
+template <int N, class F>
+KA_DEV void static_for(F&& f) {
+  static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// wait until at most N of the wave's vector-memory operations (LDS-DMA pieces included) are in flight.
+// LDS-DMA pieces do not always complete in issue order, so only N = 0 proves that a piece has landed
+// (see the wait schedules in both files).
+template <int N>
+KA_DEV void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// dispatch index -> logical index, XCD-contiguous (bijective over the grid: consecutive logical
+// indices run on one XCD and share its L2)
+KA_DEV int xcd_logical(int bid, int nwg) {
+  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+// logical tile -> (m tile, n tile): GM m-tiles x all n-tiles super-rows
+KA_DEV void tile_of(int L, int tiles_m, int tiles_n, int gm, int& tm, int& tn) {
+  const int per = gm * tiles_n;
+  const int g = L / per, first = g * gm;
+  const int rows = min(gm, tiles_m - first);
+  const int in = L - g * per;
+  tm = first + in % rows;
+  tn = in / rows;
+}
+
+// ---- host side ------------------------------------------------------------------------------------
+// compute units of the current device (256 if the query fails), asked once per source file
+static inline int ka_num_cus() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+  }
+  return n;
+}
+
+// Launchers called from another source file: the definer and the caller compile against this line.
+// Y[mn] = bf16(sum_k P[k][mn]) (gemm_skinny.hip; gemm_mfma.hip's EPI_P32 path with an output)
+extern "C" void ka_splitk_reduce_launch(bf16_t* Y, const float* P, int split, long mn, hipStream_t stream);
+// per-slice (max, index) partials -> winner per row (sampling.hip; gemm_big.hip's fused LM head)
+extern "C" int ka_argmax_finish(int* out_idx, float* out_val, const float* part_val, const int* part_idx, int rows,
+                                int slices, int vocab_offset, hipStream_t stream);

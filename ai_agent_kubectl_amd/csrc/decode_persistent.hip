@@ -211,36 +211,8 @@ KA_DEV void wait_grid(const int* sync, int nbar, int G, int* err) {
   __syncthreads();
 }
 
-KA_DEV uint4 ld_w(const bf16_t* p) {
-  return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
-}
-
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-KA_DEV float dot8(uint4 w, uint4 x, float acc) {
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, w.x), __builtin_bit_cast(bf16x2v, x.x), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, w.y), __builtin_bit_cast(bf16x2v, x.y), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, w.z), __builtin_bit_cast(bf16x2v, x.z), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, w.w), __builtin_bit_cast(bf16x2v, x.w), acc, false);
-  return acc;
-}
-
-// P re-layout scratch of the leader's MFMA attention (the scheme of csrc/attention.hip): the
-// probabilities leave the MFMA C layout (lane (col, g) holds rows 4 g + r, keys col and 16 + col) and
-// are re-read in the A layout (lane holds row col, keys 8 g .. 8 g + 7); 16 rows x PSTR bf16 per wave,
-// 16-B chunk c of row x at slot c ^ p_slot_xor(x >> 2): conflict-free stores and reads.
-constexpr int PSTR = 40;
-KA_DEV int p_slot_xor(int q) { return (q ^ (q >> 1)) & 1; }
-KA_DEV void p_store(bf16_t* pw, int prow, int col, float p0, float p1) {
-  const float q0 = dpp_f<0xB1>(p0), q1 = dpp_f<0xB1>(p1);   // lane ^ 1
-  const bool even = (col & 1) == 0;
-  const int key = even ? col : 15 + col;
-  const uint32_t v = even ? pack2(p0, q0) : pack2(q1, p1);
-  const int slot = (key >> 3) ^ p_slot_xor(prow >> 2);
-  *reinterpret_cast<uint32_t*>(pw + prow * PSTR + (slot << 3) + (key & 7)) = v;
-}
-KA_DEV bf16x8 p_load(const bf16_t* pw, int col, int g) {
-  return as_bf16x8(*reinterpret_cast<const uint4*>(pw + col * PSTR + ((g ^ p_slot_xor((col >> 2) & 3)) << 3)));
-}
+// The GEMV phases use common.h's dot8; the leader's MFMA attention re-lays P through common.h's
+// per-wave scratch (PSTR, p_store, p_load).
 
 // Sum over the 64 lanes as a wave-uniform value: the 16-lane rows by DPP, the four row sums by
 // v_readlane (no LDS round trip, unlike __shfl_xor's ds_bpermute)
@@ -971,16 +943,6 @@ __global__ __launch_bounds__(256) void zero_sync_kernel(int* __restrict__ sync) 
   for (int i = threadIdx.x; i < SYNC_BYTES / 4; i += 256) sync[i] = 0;
 }
 
-static int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 }  // namespace pd
 
 // Workspace bytes for up to MAXB sequences: residual (fp32 B H) + qkv + attn + act (bf16) + the sync words.
@@ -1061,7 +1023,7 @@ extern "C" int ka_decode_persistent_tp(void* h_out, const void* h0, const void* 
       H > 16384 ||   // rmsnorm_to_lds holds a row in 8 16-B words per thread
       ws == nullptr || B > ka_decode_persistent_max_b2(H, hq, I, hq / hkv) || (B > 1 && bt_stride <= 0))
     return (int)hipErrorInvalidValue;
-  int cus = pd::num_cus();
+  int cus = ka_num_cus();
   if (const char* e = getenv("KA_PD_GRID")) cus = std::min(cus, std::max(1, atoi(e)));
   const int G = (std::min(cus, pd::XR_MAX_WG) / hkv) * hkv;
   if (G < hkv) return (int)hipErrorInvalidValue;

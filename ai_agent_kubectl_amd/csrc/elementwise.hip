@@ -17,18 +17,7 @@
 // holds `split` fp32 partial slabs of [rows, hidden] (gemm_skinny / gemm_mfma with no output), so
 // the projection's reduce kernel and its bf16 round trip through HBM disappear.
 // PT: element type of the split-K slices P (float, or bf16_t from gemm_mfma EPI_P16).
-template <typename PT>
-KA_DEV void ld_part8(const PT* p, f32x4& s0, f32x4& s1) {
-  if constexpr (sizeof(PT) == 4) {
-    s0 = *reinterpret_cast<const f32x4*>(p);
-    s1 = *reinterpret_cast<const f32x4*>(p + 4);
-  } else {
-    const uint4 q = *reinterpret_cast<const uint4*>(p);
-    s0 = f32x4{lo_f(q.x), hi_f(q.x), lo_f(q.y), hi_f(q.y)};
-    s1 = f32x4{lo_f(q.z), hi_f(q.z), lo_f(q.w), hi_f(q.w)};
-  }
-}
-
+//
 // Every load a thread needs (its split-K slices, the residual, the norm weight) is issued before the
 // first use: up to UNR slices unrolled, further slices UNR at a time.  A rolled slice loop
 // waited for each slice before issuing the next, so a split-4 norm paid ~6 serial memory latencies.

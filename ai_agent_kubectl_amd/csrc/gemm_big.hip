@@ -50,7 +50,6 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <utility>
 
 
 namespace gb {
@@ -123,17 +122,9 @@ struct Args {
 //    register allocator rotate the 64 accumulators through VGPRs (~100 v_accvgpr moves per k-tile
 //    at this register pressure).  An MFMA's D read by anything but the next MFMA's C needs the wait
 //    states of mfma_drain() (hipcc pads nothing inside asm).
-// compile-time unrolled loop: f(std::integral_constant<int, 0>{}) ... f(..N-1): asm immediates
-// ("i" operands) need constants, which a #pragma-unrolled loop variable is not
-template <class F, int... S>
-KA_DEV void static_for_impl(F&& f, std::integer_sequence<int, S...>) {
-  (f(std::integral_constant<int, S>{}), ...);
-}
-template <int N, class F>
-KA_DEV void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
+// The unrolled loops are common.h's static_for, whose constant index gives the asm its immediates.
 
+// Not to be merged with gemm_mfma.hip's lds_rd: that one has a "memory" clobber, this one has none.
 template <int OFF>
 KA_DEV void ds_read16(bf16x8& dst, uint32_t addr) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
@@ -170,33 +161,18 @@ KA_DEV void mfma_drain() { asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "mem
 // stale: 5/40 launches at M = 4096, N = 1152 with clamped duplicate rows, 1/80 at M = 2944, N = 6144 with
 // distinct rows), and a vmcnt(0) drain in the same places never failed (0/160, clamped rows included):
 // profiles/r5/gemm_big_clamp/.  So every LDS-DMA wait of this kernel is vmcnt(0), placed where the
-// only pieces in flight are the ones about to be read (barrier #1 of `iter`).
-template <int N>
-KA_DEV void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// only pieces in flight are the ones about to be read (barrier #1 of `iter`): wait_vm<0> (common.h).
 KA_DEV void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 template <int N>
 KA_DEV void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
+// Not to be merged with gemm_mfma.hip's block_sync: this s_barrier is asm, that one the builtin.
 KA_DEV void block_sync() {
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("s_barrier" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// dispatch index -> logical index, XCD-contiguous (bijective over the grid: consecutive logical
-// indices run on one XCD and share its L2)
-KA_DEV int xcd_logical(int bid, int nwg) {
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-// logical tile -> (m tile, n tile): GM m-tiles x all n-tiles super-rows
-KA_DEV void tile_of(int L, int tiles_m, int tiles_n, int gm, int& tm, int& tn) {
-  const int per = gm * tiles_n;
-  const int g = L / per, first = g * gm;
-  const int rows = min(gm, tiles_m - first);
-  const int in = L - g * per;
-  tm = first + in % rows;
-  tn = in / rows;
-}
+// Work units map to tiles by common.h's xcd_logical and tile_of.
 
 // 16-B store / load of the tail hand-off: sc1 (write-through) asm stores and sc1 asm loads, no fence
 // (MI355X_MICROARCH.md hand-off table, row 1: one signalling lane per storing wave, per-wave counter,
@@ -808,16 +784,6 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args a) {
   wait_vm<0>();   // the trailing re-stage DMA: nothing may land in LDS after the workgroup ends
 }
 
-static int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 // Workspace of the split tail: [err + pad 256 B][counters: TAIL_MAX_TILES x 4 waves x 2][slabs]
 constexpr int TAIL_MAX_TILES = 1024;
 constexpr size_t TAIL_HDR = 256 + (size_t)TAIL_MAX_TILES * 8 * 4;
@@ -894,7 +860,7 @@ static int launch(const Args& a0, hipStream_t st, void* ws = nullptr, size_t ws_
   const int split = (EPI == EPI_P32 || EPI == EPI_P16) ? a.split : 1;
   const int tiles = a.tiles_m * a.tiles_n;
   // one workgroup per CU (the LDS allows no more); a persistent grid is a multiple of 8 (XCDs)
-  const int cus = num_cus() & ~7;
+  const int cus = ka_num_cus() & ~7;
   int total = tiles * split;
   a.full = tiles;
   a.tail_s = 1;
@@ -937,7 +903,7 @@ static int launch_grouped(const Args& a0, hipStream_t st) {
   a.tail_s = 1;
   a.tail_tiles = 0;
   a.span = 0;
-  const int cus = num_cus() & ~7;
+  const int cus = ka_num_cus() & ~7;
   const int total = a.full;
   hipLaunchKernelGGL(kern, dim3(total <= cus ? total : cus), dim3(NT), Geo<8>::LDS_TOTAL, st, a);
   return (int)hipGetLastError();
@@ -946,7 +912,7 @@ static int launch_grouped(const Args& a0, hipStream_t st) {
 template <int EPI>
 static int launch_tn(const Args& a, hipStream_t st, void* ws, size_t ws_bytes) {
   if constexpr (EPI == EPI_BF16 || EPI == EPI_ADD) {
-    if (choose_tn(a.M, a.N, EPI, num_cus() & ~7) == 6) return launch<EPI, 6>(a, st, ws, ws_bytes);
+    if (choose_tn(a.M, a.N, EPI, ka_num_cus() & ~7) == 6) return launch<EPI, 6>(a, st, ws, ws_bytes);
   }
   return launch<EPI, 8>(a, st, ws, ws_bytes);
 }
@@ -1011,7 +977,7 @@ extern "C" size_t ka_gemm_big_ws_bytes() { return gb::TAIL_HDR + (size_t)512 * g
 
 // The split that ka_gemm_big would use (tests / diagnostics): tail_s, and the whole / tail tile counts.
 extern "C" int ka_gemm_big_plan(int M, int N, int epi, int K, size_t ws_bytes, int* full, int* tail) {
-  const int G = gb::num_cus() & ~7;
+  const int G = ka_num_cus() & ~7;
   const int TN = gb::choose_tn(M, N, epi, G);
   const int tm = (M + gb::BM - 1) / gb::BM, tn = epi == gb::EPI_SWIGLU ? N / 256 : (N + 32 * TN - 1) / (32 * TN);
   if (TN != 8) {   // no split tail on 192-wide tiles (launch)
@@ -1023,7 +989,7 @@ extern "C" int ka_gemm_big_plan(int M, int N, int epi, int K, size_t ws_bytes, i
 }
 
 // The tile width ka_gemm_big runs (M, N, epi) with: 8 (256 W rows) or 6 (192 W rows).
-extern "C" int ka_gemm_big_tn(int M, int N, int epi) { return gb::choose_tn(M, N, epi, gb::num_cus() & ~7); }
+extern "C" int ka_gemm_big_tn(int M, int N, int epi) { return gb::choose_tn(M, N, epi, ka_num_cus() & ~7); }
 
 // Error word of the split tail (a slice that waited ~0.1 s for the others); cleared by the read.
 extern "C" int ka_gemm_big_err(void* ws, hipStream_t stream) {
@@ -1050,9 +1016,6 @@ extern "C" int ka_gemm_big_splitk(void* P, const void* X, const void* W, int M, 
   a.P = P;
   return bf16_out ? gb::launch<gb::EPI_P16, 8>(a, stream) : gb::launch<gb::EPI_P32, 8>(a, stream);
 }
-
-extern "C" int ka_argmax_finish(int* out_idx, float* out_val, const float* part_val, const int* part_idx, int rows,
-                                int slices, int vocab_offset, hipStream_t stream);
 
 // Workspace bytes of ka_gemm_big_argmax: per-row, per-tile (max, index).
 extern "C" size_t ka_gemm_big_argmax_ws(int M, int N) { return (size_t)M * ((N + gb::BN - 1) / gb::BN) * 8; }

@@ -30,8 +30,6 @@
 // codegen: profiles/r5/mfma_rate/)
 #include "common.h"
 
-#include <utility>
-
 namespace gm {
 
 constexpr int BK = 64;
@@ -87,11 +85,7 @@ KA_DEV void glds16(const void* g, void* l) {
                                    (__attribute__((address_space(3))) void*)l, 16, 0, AUX);
 }
 
-template <int N>
-KA_DEV void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
+// Not to be merged with gemm_big.hip's block_sync: this s_barrier is the builtin, that one asm.
 KA_DEV void block_sync() {
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
@@ -99,21 +93,12 @@ KA_DEV void block_sync() {
 }
 
 // fragment read in asm with an immediate offset: the compiler neither sees it nor counts it, so the
-// k-loop's counted lgkmcnt waits (wait_frags) are the whole synchronisation of the fragment registers
+// k-loop's counted lgkmcnt waits (wait_frags) are the whole synchronisation of the fragment registers.
+// Not to be merged with gemm_big.hip's ds_read16: this one has a "memory" clobber, that one has none.
 template <int OFF>
 KA_DEV void lds_rd(bf16x8& d, uint32_t addr) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(OFF) : "memory");
 }
-// fragments f[I..N) of one k-half: lds_rd at BASE + I * STRIDE (compile-time immediates)
-template <int I, int N, int STRIDE, int BASE>
-struct RdFrags {
-  static KA_DEV void run(bf16x8* f, uint32_t a) {
-    if constexpr (I < N) {
-      lds_rd<BASE + I * STRIDE>(f[I], a);
-      RdFrags<I + 1, N, STRIDE, BASE>::run(f, a);
-    }
-  }
-};
 
 struct Args {
   const bf16_t* X;   // [M, ldx]
@@ -131,18 +116,6 @@ struct Args {
   // are interleaved in 16-row chunks: the DMA sources gather the interleaved order (0: interleaved)
   int swi;
 };
-
-// logical tile -> (m tile, n tile): XCD-contiguous, then GM m-tiles x all n-tiles super-rows
-KA_DEV void tile_of(int bid, int nwg, int tiles_m, int tiles_n, int gm, int& tm, int& tn) {
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  const int per = gm * tiles_n;
-  const int g = L / per, first = g * gm;
-  const int rows = min(gm, tiles_m - first);
-  const int in = L - g * per;
-  tm = first + in % rows;
-  tn = in / rows;
-}
 
 // grouped GEMMs: global row chunk `c` (of BM rows, over all groups in order) -> its group's weights,
 // output-row list and row count; false past the last group's rows
@@ -205,7 +178,7 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(Args a) {
     // uniform: a block past the last group's rows leaves before any LDS / barrier use
     if (!group_chunk<C::BM>(a, blockIdx.y, Wg, rows_of, nrows, tmi)) return;
   } else {
-    tile_of(blockIdx.x, gridDim.x, a.tiles_m, a.tiles_n, a.gm, tmi, tni);
+    tile_of(xcd_logical(blockIdx.x, gridDim.x), a.tiles_m, a.tiles_n, a.gm, tmi, tni);
   }
   const int n0 = tni * C::BN, m0 = tmi * C::BM;
   const int kb = blockIdx.z * a.kps;
@@ -311,8 +284,9 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(Args a) {
     for (int kk = 0; kk < C::KT / 32; ++kk) {
       const uint32_t aA = base + (uint32_t)(rdA + (kk ? ch1 : ch0));
       const uint32_t aB = base + (uint32_t)(rdB + (kk ? ch1 : ch0));
-      RdFrags<0, C::TN, 16 * C::RB, 0>::run(fa[kk], aA);
-      RdFrags<0, C::TM, 16 * C::RB, C::A_BYTES>::run(fb[kk], aB);
+      // fragment i of a k-half sits 16 staged rows after fragment i - 1: compile-time immediates
+      static_for<C::TN>([&](auto i) { lds_rd<i * 16 * C::RB>(fa[kk][i], aA); });
+      static_for<C::TM>([&](auto i) { lds_rd<C::A_BYTES + i * 16 * C::RB>(fb[kk][i], aB); });
     }
   };
   // the fragment registers of k-half kk are operands of the wait, so no MFMA reading them is
@@ -491,7 +465,7 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(Args a) {
     tni = blockIdx.x;
     if (!group_chunk<PP::BM>(a, blockIdx.y, Wg, rows_of, nrows, tmi)) return;
   } else {
-    tile_of(blockIdx.x, gridDim.x, a.tiles_m, a.tiles_n, a.gm, tmi, tni);
+    tile_of(xcd_logical(blockIdx.x, gridDim.x), a.tiles_m, a.tiles_n, a.gm, tmi, tni);
   }
   const int n0 = tni * PP::BN, m0 = tmi * PP::BM;
   const int kb = blockIdx.z * a.kps;
@@ -791,8 +765,6 @@ extern "C" int ka_gm_bm(int cfg) {
 // 3: SwiGLU of interleaved gate/up rows -> Y [M, ldy] with N / 2 columns.
 // Requirements: K % (64 * split) == 0 (kps = K / split), N % 16 == 0, 16-B aligned rows
 // (ldx % 8 == 0); epi 3 needs N % 32 == 0 and split == 1.
-extern "C" void ka_splitk_reduce_launch(bf16_t* Y, const float* P, int split, long mn, hipStream_t stream);
-
 // epi 1 with Y != nullptr: the fp32 slabs are then reduced into Y [M, N] (ldy == N) by splitk_reduce.
 extern "C" int ka_gemm_mfma(void* Y, void* P, const void* X, const void* W, int M, int N, int K, int ldx, int ldy,
                             int split, int cfg, int epi, int gm, hipStream_t stream) {

@@ -317,7 +317,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_scalar_kernel(bf16_t* __res
   }
 }
 
-// Y[mn] = sum_k P[k][mn] in bf16 (also gemm_mfma.hip's EPI_P32 path with an output)
+// Y[mn] = sum_k P[k][mn] in bf16 (also gemm_mfma.hip's EPI_P32 path with an output: declared in common.h)
 extern "C" void ka_splitk_reduce_launch(bf16_t* Y, const float* P, int split, long mn, hipStream_t stream) {
   if (mn % 4 != 0) {
     long blocks = (mn + 255) / 256;
@@ -332,19 +332,10 @@ extern "C" void ka_splitk_reduce_launch(bf16_t* Y, const float* P, int split, lo
 
 // Row-streaming GEMV for M <= 16: each wave owns RW consecutive weight rows, i.e. one contiguous
 // RW x klen block of W, and streams it 1 KB per load instruction (64 lanes x 16 B along K) through
-// a RING-deep register ring; the dot products run on v_dot2c_f32_bf16 against the workgroup's
+// a RING-deep register ring; the dot products (dot8) run on v_dot2c_f32_bf16 against the workgroup's
 // LDS-staged X slice, and each finished row is summed across the wave (xor shuffles).  Against
 // gemv_ring_kernel (16 rows x 128 B per load, MFMA with one live row) this issues HBM-friendly
 // sequential streams and lets the grid be sized by rows per wave instead of 64-row tiles.
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-KA_DEV float dot8(uint4 w, uint4 x, float acc) {
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, w.x), __builtin_bit_cast(bf16x2v, x.x), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, w.y), __builtin_bit_cast(bf16x2v, x.y), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, w.z), __builtin_bit_cast(bf16x2v, x.z), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, w.w), __builtin_bit_cast(bf16x2v, x.w), acc, false);
-  return acc;
-}
-
 template <bool NT>
 KA_DEV uint4 ld_w16(const bf16_t* p) {
   if constexpr (NT) return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
