@@ -25,6 +25,7 @@ import torch
 from ..models.config import ModelConfig
 from .. import ops
 from ..models.llama import SAMP_WORDS, AttnMeta, LlamaModel, SampleArrays
+from ..ops.autotune import tune_engine
 
 logger = logging.getLogger("app.engine")
 from ..parallel.comm import LocalComm
@@ -221,204 +222,13 @@ class ModelRunner:
         self.d_samp.copy_(hb, non_blocking=True)
         return SampleArrays.from_image(self.d_samp, self.bmax, rows)
 
-    def autotune(self) -> dict:
-        """Pick hipBLASLt vs the hand-written decode GEMM per (bucket, N, K) on this model's weights."""
-        if self.device.type != "cuda":
-            return {}
-        from ..ops.autotune import tune_linear
-        groups = {}
-        norm_fed = set()
-        # O / down partials feed the norm directly at TP = 1, and in a TP rank's decode step when the
-        # collective reduces them (models/llama.py `fuse`): timed with that consumer
-        local = getattr(self.model, "_local_comm", False) or getattr(self.model.comm, "splitk_norm", False)
-        for L in self.model.layers:
-            for k in ("wqkv", "wo", "w13", "w2"):
-                w = L.get(k)
-                if w is not None and w.dim() == 2:
-                    groups.setdefault(tuple(w.shape), []).append(w)
-                    if local and k in ("wo", "w2"):   # llama.py defers their split-K reduce into the norm
-                        norm_fed.add(tuple(w.shape))
-        lm = self.model.W["lm_head"]
-        groups.setdefault(tuple(lm.shape), []).append(lm)
-        consumers = {}
-        m = self.model
-        if m.fuse_decode_rope and m.D == 128 and self.block_size == 16 and "wqkv" in m.layers[0]:
-            # QKV is timed with its real consumer, the fused RoPE + KV append + decode attention
-            # on a synthetic 128-token context (a norm stand-in picked a split plan whose partials
-            # then slowed the attention prologue: profiles/phase_profile_c256_qkv_proxy_negative.txt)
-            consumers[tuple(m.layers[0]["wqkv"].shape)] = (self._attention_consumer(), m.bf16_qkv_partials)
-        bf16 = getattr(self.model, "bf16_partials", False)
-        ctx_of = {nk: ("attn" + ("-bf16" if consumers[nk][1] else "")) if nk in consumers else
-                  ("norm" + ("-bf16" if bf16 else "")) if nk in norm_fed else "plain" for nk in groups}
-        from ..ops import TILE_MAX_M
-        from ..ops.autotune import DEFAULT_PLAN_FILE, load_plan, save_plan
-        wanted = {(M, N, K): ctx_of[(N, K)] for (N, K) in groups for M in set(self.buckets) if M <= TILE_MAX_M}
-        mode = os.environ.get("KA_GEMM_PLAN", "file")
-        path = os.environ.get("KA_GEMM_PLAN_FILE", DEFAULT_PLAN_FILE)
-        Ms = self.buckets
-        if mode == "file":
-            missing = load_plan(path, wanted)
-            if not missing:
-                return {"from": path}
-            Ms = sorted({M for (M, _, _) in missing})
-            groups = {nk: ws for nk, ws in groups.items() if any((M,) + nk in missing for M in Ms)}
-        report = tune_linear(groups, Ms, norm_fed, bf16, consumers)
-        if mode == "write":
-            save_plan(path, report, ctx_of)
-        return report
-
-    @torch.inference_mode()
-    def tune_lm_head(self) -> dict:
-        """Per decode bucket: the fused LM head + masked argmax (csrc/gemm_big.hip) against the
-        GEMM plan's LM head + masked_argmax, on the model's own LM head and a SAFE_DECODE mask row;
-        fills ops.LM_HEAD_FUSED and the threshold for untimed row counts."""
-        m = self.model
-        lm = m.W["lm_head"]
-        if self.device.type != "cuda" or ops.LM_HEAD_MODE != "auto":
-            return {}
-        from ..ops.autotune import _time, load_section, plan_mode, save_section
-        K = lm.shape[1]
-        report = {}
-        # persisted with the GEMM plan (ops/tuned/gemm_plan_mi355x.json, section lm_head): the same
-        # decision on every box and run unless KA_GEMM_PLAN=tune / write re-times it
-        mode, path = plan_mode()
-        key = lambda M: f"{M},{lm.shape[0]},{K},{int(self.mask_bits is not None)}"   # noqa: E731
-        saved = load_section(path, "lm_head") if mode == "file" else {}
-        for M in sorted(set(self.buckets)):
-            x = torch.randn(M, K, device=self.device, dtype=lm.dtype)
-            if not ops.lm_head_argmax_ok(x, lm, m.vocab_offset):
-                return {}
-            if key(M) in saved:
-                fused, t_fu, t_un = saved[key(M)]
-            else:
-                midx = (torch.zeros(M, dtype=torch.int32, device=self.device) if self.mask_bits is not None else None)
-                t_un = _time(lambda w: ops.masked_argmax(ops.linear(x, w), self.mask_bits, midx, m.vocab_offset), [lm])
-                t_fu = _time(lambda w: ops.lm_head_argmax(x, w, self.mask_bits, midx, m.vocab_offset), [lm])
-                # within the plan's margin the hand-written fused kernel is taken over a hipBLASLt plan
-                # (ops/autotune.py BLAS_MARGIN), as for the GEMM plan and the decode SwiGLU
-                from ..ops.autotune import BLAS_MARGIN
-                plan = ops.GEMM_PLAN.get((M, lm.shape[0], K), ("blas",))
-                fused = t_fu < t_un * (1.0 + (BLAS_MARGIN if plan[0] == "blas" else 0.0))
-            ops.LM_HEAD_FUSED[M] = bool(fused)
-            report[M] = {"fused_us": round(t_fu, 1), "unfused_us": round(t_un, 1), "fused": bool(fused)}
-        if mode == "write":
-            save_section(path, "lm_head", {key(M): [r["fused"], r["fused_us"], r["unfused_us"]]
-                                          for M, r in report.items()})
-        wins = sorted(M for M, f in ops.LM_HEAD_FUSED.items() if f)
-        # untimed row counts: fused from the smallest bucket above which every timed bucket won
-        ops.LM_HEAD_FUSED_MIN_M = next((M for M in wins if all(ops.LM_HEAD_FUSED[b] for b in ops.LM_HEAD_FUSED
-                                                                  if b >= M)), 1 << 30)
-        logger.info("lm head plan: %s (fused from %d rows)", report, ops.LM_HEAD_FUSED_MIN_M)
-        return report
-
-    @torch.inference_mode()
-    def tune_prefill(self) -> dict:
-        """Prefill / mixed-step projections (ops.PREFILL_GEMM auto): csrc/gemm_big.hip against hipBLASLt
-        per (N, K) of the model's QKV / O / down at the row-count buckets of ops.PREFILL_BUCKETS, on
-        the model's own weights rotated over layers (the persisted decision in the plan file, section
-        prefill, unless KA_GEMM_PLAN=tune / write).  Fills ops.PREFILL_PLAN: gemm_big where it is within
-        KA_PREFILL_MARGIN (default 0.02) of hipBLASLt."""
-        m = self.model
-        ops.PREFILL_PLAN.clear()
-        if self.device.type != "cuda" or ops.PREFILL_GEMM != "auto":
-            return {}
-        from ..ops.autotune import _time, load_section, plan_mode, save_section
-        margin = float(os.environ.get("KA_PREFILL_MARGIN", "0.02"))
-        groups = {}
-        for L in m.layers:
-            for k in ("wqkv", "wo", "w2"):
-                w = L.get(k)
-                if w is not None and w.dim() == 2:
-                    groups.setdefault(tuple(w.shape), []).append(w)
-        mode, path = plan_mode()
-        saved = load_section(path, "prefill") if mode == "file" else {}
-        report = {}
-        for (N, K), ws in groups.items():
-            ws = ws[:4]
-            for M in ops.PREFILL_BUCKETS:
-                key = f"{M},{N},{K}"
-                if key in saved:
-                    big, t_big, t_blas = saved[key]
-                else:
-                    x = torch.randn(M, K, device=self.device, dtype=ws[0].dtype)
-                    if not ops.big_gemm_ok(x, ws[0]):
-                        break
-                    t_blas = _time(lambda w: torch.nn.functional.linear(x, w), ws, reps=6)
-                    t_big = _time(lambda w: ops.linear_big(x, w), ws, reps=6)
-                    big = t_big <= t_blas * (1.0 + margin)
-                    del x
-                ops.PREFILL_PLAN[(M, N, K)] = bool(big)
-                report[key] = [bool(big), round(float(t_big), 1), round(float(t_blas), 1)]
-        if mode == "write":
-            save_section(path, "prefill", report)
-        logger.info("prefill gemm plan: %s", report)
-        return report
-
-    @torch.inference_mode()
-    def tune_swiglu(self) -> dict:
-        """Per decode bucket: gate_up with the ring kernel's SwiGLU epilogue (ops.linear_gm_swiglu,
-        each configuration) against the GEMM plan's gate_up + SiLU·mul, on the model's own w13
-        rotated over layers; fills ops.DECODE_SWIGLU_CFG with the winners."""
-        m = self.model
-        ops.DECODE_SWIGLU_CFG.clear()
-        if self.device.type != "cuda" or ops.DECODE_SWIGLU == "0" or getattr(m.cfg, "is_moe", False):
-            return {}
-        ws = [L["w13"] for L in m.layers if L.get("w13") is not None and L["w13"].dim() == 2][:8]
-        if not ws:
-            return {}
-        w2s = [L["w2"] for L in m.layers if L.get("w2") is not None and L["w2"].dim() == 2][:8]
-        from ..ops.autotune import _time, load_section, plan_mode, save_section
-        report = {}
-        mode, path = plan_mode()   # persisted like the GEMM plan (section decode_swiglu)
-        key = lambda M: f"{M},{ws[0].shape[0]},{ws[0].shape[1]}"   # noqa: E731
-        saved = load_section(path, "decode_swiglu") if mode == "file" else {}
-        for M in sorted(set(self.buckets)):
-            x = torch.randn(M, ws[0].shape[1], device=self.device, dtype=ws[0].dtype)
-            if not ops.decode_swiglu_ok(x, ws[0]):
-                continue
-            if key(M) in saved:
-                cfg, t_fu, t_un = saved[key(M)]
-                best = (int(cfg), t_fu if int(cfg) else t_un)
-                fused = (int(cfg), t_fu)
-            else:
-                small = M <= ops.GEMV_SWIGLU_MAX_M and len(w2s) == len(ws)
-                if small:
-                    # the unfused path at these rows computes SiLU·mul inside the down GEMV's staging
-                    # (ops.swiglu_linear): compare gate_up + down, both ways (indices pair w13 / w2)
-                    pair = {id(a): b for a, b in zip(ws, w2s)}
-                    t_un = _time(lambda w: ops.swiglu_linear(ops.linear(x, w, defer_reduce=True), pair[id(w)]), ws)
-                else:
-                    t_un = _time(lambda w: ops.silu_mul(ops.linear(x, w, defer_reduce=True)), ws)
-                fused = (0, float("inf"))
-                cands = list(ops.DECODE_SWIGLU_CFGS)
-                if M >= ops.BIG_PLAN_MIN_M and ops.swiglu_gemm_ok(x, ws[0]):
-                    cands.append(ops.DECODE_SWIGLU_BIG)   # csrc/gemm_big.hip's SwiGLU epilogue
-                for cfg in cands:
-                    if small:
-                        t = _time(lambda w: ops.linear(ops.linear_gm_swiglu(x, w, cfg), pair[id(w)]), ws)
-                    else:
-                        t = _time(lambda w: ops.linear_gm_swiglu(x, w, cfg), ws)
-                    if t < fused[1]:
-                        fused = (cfg, t)
-                # the unfused path's gate_up is a hipBLASLt plan: the hand-written fused kernel is
-                # taken within the plan's margin too (ops/autotune.py BLAS_MARGIN)
-                from ..ops.autotune import BLAS_MARGIN
-                plan = ops.GEMM_PLAN.get((M, ws[0].shape[0], ws[0].shape[1]), ("blas",))
-                margin = BLAS_MARGIN if plan[0] == "blas" else 0.0
-                best = fused if fused[1] < t_un * (1.0 + margin) else (0, t_un)
-            ops.DECODE_SWIGLU_CFG[M] = best[0]   # 0 (unfused) is kept too: un-timed M take the next bucket
-            # fused_us: the fastest SwiGLU-epilogue configuration's time, whether or not it was taken
-            report[M] = {"cfg": best[0], "fused_us": round(fused[1], 1), "unfused_us": round(t_un, 1)}
-        if mode == "write":
-            save_section(path, "decode_swiglu", {key(M): [r["cfg"], r["fused_us"], r["unfused_us"]]
-                                                for M, r in report.items()})
-        logger.info("decode swiglu plan: %s", report)
-        return report
-
     def _attention_consumer(self, ctx: int = 128):
         """fn(qkv, M): decode_attention_rope over M synthetic sequences of `ctx` cached tokens in
-        layer 0's cache (autotune runs before serving: the KV written here is never read)."""
+        layer 0's cache (tuning runs before serving: the KV written here is never read), for
+        tune_gemm_plan to time QKV with; None where that kernel cannot read this cache (16-token blocks)."""
         m, bs = self.model, self.block_size
+        if bs != 16:
+            return None
         nb = (ctx + bs - 1) // bs
         memo = {}
 
@@ -443,10 +253,7 @@ class ModelRunner:
         if self.device.type == "cuda":
             ops.gemm_big_ws(self.device)   # allocated (and zeroed) outside any capture
         if autotune:
-            self.gemm_plan = self.autotune()
-            self.lm_head_plan = self.tune_lm_head()
-            self.swiglu_plan = self.tune_swiglu()
-            self.prefill_plan = self.tune_prefill()
+            self.plans = tune_engine(self.model, self.buckets, self.mask_bits, self._attention_consumer())
         self.h_np[:] = 0
         o = self._off
         for name in ("slots",):

@@ -207,7 +207,7 @@ class LlamaModel:
                 h = ops.linear(ops.linear_swiglu(x, L["w13"]), L["w2"], defer_reduce=fuse,
                                bf16_partials=self.bf16_partials)
             elif sw := ops.decode_swiglu_cfg(x, L["w13"]):
-                # decode buckets where the ring kernel's SwiGLU epilogue won (ModelRunner.tune_swiglu)
+                # decode buckets where the ring kernel's SwiGLU epilogue won (ops.autotune.tune_decode_swiglu)
                 h = ops.linear(ops.linear_gm_swiglu(x, L["w13"], sw), L["w2"], defer_reduce=fuse,
                                bf16_partials=self.bf16_partials)
             else:

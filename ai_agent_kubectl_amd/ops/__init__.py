@@ -412,7 +412,7 @@ def lm_head_argmax_ok(x: torch.Tensor, w: torch.Tensor, vocab_offset: int = 0) -
             and w.shape[0] % 128 == 0 and w.is_contiguous() and vocab_offset % 4 == 0)
 
 
-# Fused LM head per row count M: filled at engine start by ModelRunner.tune_lm_head (timed against
+# Fused LM head per row count M: filled at engine start by ops.autotune.tune_lm_head (timed against
 # the plan's GEMM + masked_argmax on the model's own LM head); row counts not timed (prefill / mixed
 # steps sample S rows) use the fused kernel from LM_HEAD_FUSED_MIN_M rows up.
 # KA_FUSED_LM_HEAD: auto (default) | 1 (always, where the shape allows) | 0 (never).
@@ -558,7 +558,7 @@ PREFILL_SWIGLU = os.environ.get("KA_PREFILL_SWIGLU", "1") == "1"
 PREFILL_SWIGLU_MIN_M = int(os.environ.get("KA_PREFILL_SWIGLU_MIN_M", "513"))
 # Prefill / mixed-step QKV, O and down projections (M > TILE_MAX_M): KA_PREFILL_GEMM=big runs them all
 # on csrc/gemm_big.hip (split tail, 192-wide tiles where they fill the rounds), blas all on hipBLASLt
-# (F.linear), auto (default) per shape and row-count bucket from PREFILL_PLAN: ModelRunner.tune_prefill
+# (F.linear), auto (default) per shape and row-count bucket from PREFILL_PLAN: ops.autotune.tune_prefill
 # times both on the model's own weights at engine start (persisted in the plan file, section prefill)
 # and keeps gemm_big where it is within PREFILL_MARGIN of hipBLASLt.
 PREFILL_GEMM = os.environ.get("KA_PREFILL_GEMM", "auto")
@@ -577,6 +577,9 @@ def use_big_gemm(x: torch.Tensor, w: torch.Tensor) -> bool:
     if PREFILL_GEMM == "big":
         return True
     return PREFILL_PLAN.get((prefill_bucket(x.shape[0]), w.shape[0], w.shape[1]), False)
+
+
+GB_EPI_BF16 = 0
 GB_EPI_SWIGLU = 3
 
 
@@ -646,8 +649,8 @@ def linear_big(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = N
     N = w.shape[0]
     out = torch.empty((M, N), dtype=x.dtype, device=x.device) if out is None else out
     ws = gemm_big_ws(x.device)
-    check(lib.ka_gemm_big(_p(out), None, _p(x), _p(w), M, N, K, x.stride(0), out.stride(0), 0, 0, _p(ws),
-                          ws.numel() if ws is not None else 0, _stream()), "gemm_big")
+    check(lib.ka_gemm_big(_p(out), None, _p(x), _p(w), M, N, K, x.stride(0), out.stride(0), GB_EPI_BF16, 0,
+                          _p(ws), ws.numel() if ws is not None else 0, _stream()), "gemm_big")
     return out
 
 
@@ -659,7 +662,7 @@ def big_gemm_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
 
 
 # Decode gate_up with the SwiGLU epilogue in the csrc/gemm_mfma.hip ring kernel, per decode bucket
-# M -> configuration: filled at engine start by ModelRunner.tune_swiglu where it beats the GEMM plan's
+# M -> configuration: filled at engine start by ops.autotune.tune_decode_swiglu where it beats the GEMM plan's
 # gate_up + SiLU·mul (profiles/r3/decode_swiglu: 72.9 vs 77.4 us at M = 256, 51.9 vs 58.4 at 128,
 # Llama-3-8B).  KA_DECODE_SWIGLU=0 disables it.
 DECODE_SWIGLU = os.environ.get("KA_DECODE_SWIGLU", "auto")
@@ -673,7 +676,8 @@ DECODE_SWIGLU_BIG = 100
 
 def decode_swiglu_ok(x: torch.Tensor, w13: torch.Tensor) -> bool:
     """Rows the ring kernel's SwiGLU epilogue takes: any M up to TILE_MAX_M (rows past M re-read the
-    distinct rows r % M: a clamp to row M - 1 triggered LDS-DMA corruption, profiles/r5/gemm_big_clamp/); below 8 rows ModelRunner.tune_swiglu weighs it against the GEMV path with the activation in
+    distinct rows r % M: a clamp to row M - 1 triggered LDS-DMA corruption, profiles/r5/gemm_big_clamp/);
+    below 8 rows ops.autotune.tune_decode_swiglu weighs it against the GEMV path with the activation in
     the down projection's staging (ops.swiglu_linear), down projection included."""
     M, K = x.shape
     return (x.is_contiguous() and w13.is_contiguous() and w13.shape[1] == K and K % 64 == 0
@@ -961,10 +965,10 @@ def moe_experts_grouped(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, to
               "moe_sort")
         act = torch.empty((R, I), dtype=x.dtype, device=x.device)   # expert-sorted rows
         check(lib.ka_gemm_big_grouped(_p(act), _p(xs), _p(w13), _p(tab), chunks, None, R, two_i, H, H, I, El,
-                                      3, st), "gemm_big_grouped(w13)")
+                                      GB_EPI_SWIGLU, st), "gemm_big_grouped(w13)")
         y2 = torch.empty((R, H), dtype=x.dtype, device=x.device)    # slot rows (others never read)
         check(lib.ka_gemm_big_grouped(_p(y2), _p(act), _p(w2), _p(tab), chunks, _p(slot), R, H, I, I, H, El,
-                                      0, st), "gemm_big_grouped(w2)")
+                                      GB_EPI_BF16, st), "gemm_big_grouped(w2)")
         out = torch.empty((T, H), dtype=x.dtype, device=x.device)
         check(lib.ka_moe_combine(_p(out), _p(y2), None, 1, _p(topk_w), _p(topk_ids), T, k, H, e0, El, st),
               "moe_combine")

@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ai_agent_kubectl_amd.engine.builder import EngineOptions, build_engine  # noqa: E402
 from ai_agent_kubectl_amd.engine.sequence import SamplingParams, Sequence  # noqa: E402
 from ai_agent_kubectl_amd.llm.engine_backend import EngineLLM  # noqa: E402
+from ai_agent_kubectl_amd.ops.autotune import tune_decode_swiglu, tune_gemm_plan, tune_lm_head  # noqa: E402
 
 
 def main():
@@ -44,7 +45,9 @@ def main():
     sch.gather_max_s = 0.0
     params = SamplingParams(max_new_tokens=64, ignore_eos=True)
     if args.plan_first:
-        r.gemm_plan, r.lm_head_plan, r.swiglu_plan = r.autotune(), r.tune_lm_head(), r.tune_swiglu()
+        tune_gemm_plan(r.model, r.buckets, r._attention_consumer())
+        tune_lm_head(r.model, r.buckets, r.mask_bits)
+        tune_decode_swiglu(r.model, r.buckets)
     with torch.inference_mode():
         for i in range(max(buckets)):
             sch.add(Sequence(prompt_ids=be.prompt_ids(f"list pods in namespace team-{i}"), params=params))

@@ -56,7 +56,7 @@ def main():
           flush=True)
     t0 = time.time()
     r.capture_graphs(autotune=True)
-    plan = getattr(r, "gemm_plan", {})
+    plan = getattr(r, "plans", {}).get("gemm", {})   # no plans without graphs (--device cpu)
     print(f"plans + graphs in {time.time() - t0:.1f} s; gemm plan: "
           f"{plan.get('from', 'tuned at start') if isinstance(plan, dict) else plan}", flush=True)
     if os.environ.get("PLAN_COPY_TO"):

@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ai_agent_kubectl_amd import ops  # noqa: E402
-from ai_agent_kubectl_amd.ops.autotune import DEFAULT_PLAN_FILE, _time, save_section  # noqa: E402
+from ai_agent_kubectl_amd.ops.autotune import DEFAULT_PLAN_FILE, _time_big_vs_blas, save_section  # noqa: E402
 
 
 def main():
@@ -39,10 +39,7 @@ def main():
             x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
             if not ops.big_gemm_ok(x, ws[0]):
                 continue
-            tb, tg = [], []
-            for _ in range(2):   # interleaved passes
-                tb.append(_time(lambda w: torch.nn.functional.linear(x, w), ws, reps=6, rounds=5))
-                tg.append(_time(lambda w: ops.linear_big(x, w), ws, reps=6, rounds=5))
+            tg, tb = zip(*(_time_big_vs_blas(x, ws, reps=6, rounds=5) for _ in range(2)))   # interleaved passes
             t_blas, t_big = min(tb), min(tg)
             big = t_big <= t_blas * (1.0 + args.margin)
             key = f"{M},{N},{K}"

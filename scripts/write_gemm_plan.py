@@ -18,7 +18,8 @@ import time  # noqa: E402
 import torch  # noqa: E402
 
 from ai_agent_kubectl_amd.engine.builder import EngineOptions, build_engine  # noqa: E402
-from ai_agent_kubectl_amd.ops.autotune import DEFAULT_PLAN_FILE  # noqa: E402
+from ai_agent_kubectl_amd.ops.autotune import (DEFAULT_PLAN_FILE, tune_decode_swiglu, tune_gemm_plan,  # noqa: E402
+                                               tune_lm_head, tune_prefill)
 
 
 def _heartbeat():   # big models build and tune silently for minutes
@@ -41,24 +42,24 @@ ONLY = os.environ.get("PLAN_ONLY", "")
 for model in sys.argv[1:] or ["llama3-8b"]:
     eng = build_engine(EngineOptions(model=model, device="cuda", max_batch=max(BUCKETS), graph_buckets=BUCKETS,
                                      kv_cache_tokens=65536, max_model_len=512))
-    rep = {}
+    r, rep = eng.runner, {}
     if ONLY not in ("prefill", "epilogues"):
-        rep = eng.runner.autotune()
+        rep = tune_gemm_plan(r.model, r.buckets, r._attention_consumer())
         print(model, len(rep), "plan entries", flush=True)
     if ONLY == "epilogues":   # the unfused side of each comparison runs the persisted GEMM plan
         os.environ["KA_GEMM_PLAN"] = "file"
-        print(model, "GEMM plan:", eng.runner.autotune(), flush=True)
+        print(model, "GEMM plan:", tune_gemm_plan(r.model, r.buckets, r._attention_consumer()), flush=True)
         os.environ["KA_GEMM_PLAN"] = "write"
     if ONLY not in ("prefill", "decode"):
         # the engine-start decisions persisted next to the plan (sections lm_head / decode_swiglu)
-        print("lm_head:", eng.runner.tune_lm_head(), flush=True)
-        print("decode_swiglu:", eng.runner.tune_swiglu(), flush=True)
+        print("lm_head:", tune_lm_head(r.model, r.buckets, r.mask_bits), flush=True)
+        print("decode_swiglu:", tune_decode_swiglu(r.model, r.buckets), flush=True)
     if ONLY not in ("epilogues", "decode"):
-        print("prefill:", eng.runner.tune_prefill(), flush=True)
+        print("prefill:", tune_prefill(r.model), flush=True)
     if COPY_TO:
         os.makedirs(COPY_TO, exist_ok=True)
         shutil.copy(DEFAULT_PLAN_FILE, COPY_TO)
     for k in sorted(rep):
         print(" ", k, rep[k], flush=True)
-    del eng
+    del eng, r
     torch.cuda.empty_cache()
