@@ -9,6 +9,11 @@ honoured: above temperature 0 the engine samples by seeded Gumbel-max (csrc/samp
 and the same seed, prompt and parameters give the same completion whatever else is in the batch;
 without a seed every request draws its own.  Out-of-range values get 422; temperature > 0 on a
 tensor-parallel engine gets 400.  `max_tokens` caps the completion.
+`logprobs: true` adds `choices[0].logprobs.content` in OpenAI's shape, one entry per token of the
+content, each with `top_logprobs` (0..20) alternatives (csrc/logprobs.hip).  They are the model's
+distribution under the token mask BEFORE temperature / top_p / top_k are applied (what vLLM reports by
+default), so they do not depend on those fields or on `seed`.  `top_logprobs` without `logprobs: true`
+gets 422; logprobs on a tensor-parallel engine get 400.
 Auth: when API_AUTH_KEY is set, `Authorization: Bearer <key>` or `X-API-Key: <key>`.
 """
 from __future__ import annotations
@@ -18,7 +23,7 @@ import uuid
 from typing import List, Optional
 
 from fastapi import Header, HTTPException, Request
-from pydantic import BaseModel, Field
+from pydantic import BaseModel, Field, model_validator
 
 
 class ChatMessage(BaseModel):
@@ -35,6 +40,14 @@ class ChatRequest(BaseModel):
     top_k: Optional[int] = Field(0, ge=0)
     seed: Optional[int] = None
     stream: Optional[bool] = False
+    logprobs: Optional[bool] = False
+    top_logprobs: Optional[int] = Field(None, ge=0, le=20)
+
+    @model_validator(mode="after")
+    def _top_logprobs_needs_logprobs(self):
+        if self.top_logprobs is not None and not self.logprobs:
+            raise ValueError("top_logprobs requires logprobs: true")
+        return self
 
 
 def install(app, svc, settings) -> None:
@@ -62,15 +75,25 @@ def install(app, svc, settings) -> None:
         if req.stream:
             raise HTTPException(status_code=400, detail="stream=true is not supported")
         msgs = [m.model_dump() for m in req.messages]
+        kw = dict(max_tokens=req.max_tokens or 64, temperature=req.temperature or 0.0,
+                  top_p=1.0 if req.top_p is None else req.top_p, top_k=req.top_k or 0, seed=req.seed)
+        content = None
         try:
-            text, finish, n_in, n_out = await backend.generate_chat(
-                msgs, max_tokens=req.max_tokens or 64, temperature=req.temperature or 0.0,
-                top_p=1.0 if req.top_p is None else req.top_p, top_k=req.top_k or 0, seed=req.seed)
-        except ValueError as e:   # a request this engine cannot serve (temperature > 0 under TP > 1)
+            if req.logprobs:
+                if not hasattr(backend, "generate_chat_logprobs"):
+                    raise ValueError("this backend does not report logprobs")
+                text, finish, n_in, n_out, content = await backend.generate_chat_logprobs(
+                    msgs, top_logprobs=req.top_logprobs or 0, **kw)
+            else:
+                text, finish, n_in, n_out = await backend.generate_chat(msgs, **kw)
+        except ValueError as e:   # a request this engine cannot serve (temperature > 0 / logprobs under TP > 1)
             raise HTTPException(status_code=400, detail=str(e))
+        choice = {"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": finish}
+        if content is not None:   # only when asked for: the response is otherwise what it always was
+            choice["logprobs"] = {"content": content}
         return {
             "id": "chatcmpl-" + uuid.uuid4().hex[:24], "object": "chat.completion", "created": int(time.time()),
             "model": req.model or settings.MODEL,
-            "choices": [{"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": finish}],
+            "choices": [choice],
             "usage": {"prompt_tokens": n_in, "completion_tokens": n_out, "total_tokens": n_in + n_out},
         }

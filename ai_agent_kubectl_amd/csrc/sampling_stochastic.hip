@@ -26,12 +26,10 @@
 // into slices; a row with a cut is worked by its slice-0 workgroup alone (the other slices report
 // nothing), up to five passes over a row that stays in L2.  sample_finish_kernel picks the winner of
 // the slices' partials, as argmax_finish_kernel does for the argmax.
-#include "common.h"
+#include "sampling_common.h"
 
 namespace {
 
-constexpr int SAMPLE_NT = 512;
-constexpr int SAMPLE_WAVES = SAMPLE_NT / 64;
 constexpr unsigned long long GOLDEN = 0x9E3779B97F4A7C15ull;
 
 KA_DEV unsigned long long mix64(unsigned long long z) {
@@ -48,110 +46,6 @@ KA_DEV float gumbel_u(unsigned long long key, int gid) {
 
 // logf, not __logf: the tests' score margin is derived from logf's accuracy
 KA_DEV float gumbel(float u) { return -logf(-logf(u)); }
-
-// order-preserving 16-bit key of a bf16 pattern (larger value <=> larger key); -0 counts as +0
-KA_DEV uint32_t bf16_key(uint32_t b) {
-  b = b == 0x8000u ? 0u : b;
-  return (b & 0x8000u) ? (b ^ 0xffffu) : (b | 0x8000u);
-}
-KA_DEV float key_value(uint32_t k) {
-  const uint32_t b = (k & 0x8000u) ? (k & 0x7fffu) : (k ^ 0xffffu);
-  return __uint_as_float(b << 16);
-}
-
-// f(local index, bf16 pattern, value) for every allowed token of vectors [v0, nvec) of a row, each
-// lane in increasing index order.  Batches of UN vectors per lane, as in masked_argmax_kernel: the
-// UN mask words are issued together, then the logits of the vectors with any bit set, then all are
-// scanned (one vector per iteration would wait for its mask word and then for its logits).
-template <typename F>
-KA_DEV void scan_row(const bf16_t* __restrict__ lr, const uint32_t* __restrict__ mrow, int v0, int nvec,
-                     int vocab_offset, F&& f) {
-  constexpr int UN = 8;
-  for (int v = v0 + threadIdx.x; v < nvec; v += SAMPLE_NT * UN) {
-    uint32_t bits[UN], raw[UN];
-    uint4 q[UN];
-#pragma unroll
-    for (int j = 0; j < UN; ++j) {
-      const int gb = ((v + j * SAMPLE_NT) << 3) + vocab_offset;   // the mask is indexed by the global token id
-      raw[j] = 0xffffffffu;
-      if (mrow && v + j * SAMPLE_NT < nvec) raw[j] = mrow[gb >> 5];
-    }
-#pragma unroll
-    for (int j = 0; j < UN; ++j) {
-      const int gb = ((v + j * SAMPLE_NT) << 3) + vocab_offset;
-      bits[j] = v + j * SAMPLE_NT < nvec ? (mrow ? (raw[j] >> (gb & 31)) & 0xffu : 0xffu) : 0u;
-      if (bits[j]) q[j] = *reinterpret_cast<const uint4*>(lr + ((v + j * SAMPLE_NT) << 3));
-    }
-#pragma unroll
-    for (int j = 0; j < UN; ++j) {
-      if (!bits[j]) continue;
-      const int base = (v + j * SAMPLE_NT) << 3;
-      const uint32_t w[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const uint32_t b = (k & 1) ? (w[k >> 1] >> 16) : (w[k >> 1] & 0xffffu);
-        if ((bits[j] >> k) & 1u) f(base + k, b, __uint_as_float(b << 16));
-      }
-    }
-  }
-}
-
-struct Hist {
-  uint32_t cnt[SAMPLE_WAVES][256];
-  unsigned long long mass[SAMPLE_WAVES][256];
-};
-
-KA_DEV void hist_clear(Hist& h) {
-  for (int i = threadIdx.x; i < SAMPLE_WAVES * 256; i += SAMPLE_NT) {
-    (&h.cnt[0][0])[i] = 0u;
-    (&h.mass[0][0])[i] = 0ull;
-  }
-  __syncthreads();
-}
-
-// fold the waves' private bins into copy 0 (after the barrier that ends the pass)
-KA_DEV void hist_fold(Hist& h) {
-  __syncthreads();
-  if (threadIdx.x < 256) {
-    uint32_t c = 0u;
-    unsigned long long m = 0ull;
-#pragma unroll
-    for (int w = 0; w < SAMPLE_WAVES; ++w) {
-      c += h.cnt[w][threadIdx.x];
-      m += h.mass[w][threadIdx.x];
-    }
-    h.cnt[0][threadIdx.x] = c;
-    h.mass[0][threadIdx.x] = m;
-  }
-  __syncthreads();
-}
-
-// largest (value, lowest index) of the workgroup, in thread 0
-KA_DEV void block_argmax(float& best, int& bidx, float* sb, int* si) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bidx, o, 64);
-    if (ob > best || (ob == best && oi < bidx)) {
-      best = ob;
-      bidx = oi;
-    }
-  }
-  if ((threadIdx.x & 63) == 0) {
-    sb[threadIdx.x >> 6] = best;
-    si[threadIdx.x >> 6] = bidx;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    best = sb[0];
-    bidx = si[0];
-    for (int i = 1; i < SAMPLE_WAVES; ++i)
-      if (sb[i] > best || (sb[i] == best && si[i] < bidx)) {
-        best = sb[i];
-        bidx = si[i];
-      }
-  }
-}
 
 }  // namespace
 

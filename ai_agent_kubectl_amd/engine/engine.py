@@ -34,7 +34,7 @@ from typing import Callable, Dict, List, Optional
 from .block_manager import make_block_manager
 from .runner import CollectiveTimeout, ModelRunner
 from .scheduler import Scheduler
-from .sequence import PLACEHOLDER, SamplingParams, Sequence, SeqStatus
+from .sequence import PLACEHOLDER, SamplingParams, Sequence, SeqStatus, TokenLogprob
 
 logger = logging.getLogger("app.engine")
 
@@ -162,6 +162,12 @@ class LLMEngine:
             # the vocab-parallel combine of sampled scores needs the per-row arrays on every rank: a
             # worker-protocol change that is not made yet
             raise ValueError("temperature > 0 is not supported with tensor parallelism (TP > 1)")
+        if params.logprobs is not None:
+            if not 0 <= int(params.logprobs) <= 20:
+                raise ValueError("logprobs must be None or the number of alternatives, 0..20")
+            if self.runner.tp_size > 1:
+                # the logits are vocab-parallel: the ranks' (max, mass) pairs would have to be combined
+                raise ValueError("logprobs are not supported with tensor parallelism (TP > 1)")
         seq = Sequence(prompt_ids=list(prompt_ids), params=params, callback=callback,
                        forced_prefix=list(forced_prefix or []))
         self._inbox.put(("add", seq))
@@ -330,11 +336,15 @@ class LLMEngine:
     def _settle(self, batch, tokens) -> None:
         """Placeholders of an advanced `batch` get their sampled tokens; prefix blocks are published;
         EOS / max_new_tokens finish sequences (a row a lookahead step computed for a sequence
-        finished here is discarded at that step's own readback)."""
+        finished here is discarded at that step's own readback).  The step's log-probability records
+        (the runner left them at its readback: collect / execute) are appended exactly where a token
+        is, so whatever discards a token (a finished sequence's chained successor, a partial chunk)
+        discards its record with it, and `len(seq.logprobs) == seq.num_generated` after every settle."""
         now = time.perf_counter()
         m = self.metrics
+        recs, self.runner.last_logprobs = getattr(self.runner, "last_logprobs", None), None
         prefill = {id(s) for s in batch.prefill_seqs}
-        for s, tok in zip(batch.seqs, tokens):
+        for row, (s, tok) in enumerate(zip(batch.seqs, tokens)):
             if s.finished:
                 continue
             if id(s) in batch.partial:   # a chunk of a long prompt: its KV is cached, nothing sampled
@@ -344,6 +354,12 @@ class LLMEngine:
                 continue
             s.output_ids[-1] = int(tok)
             s.ph_row = None
+            k = s.params.logprobs
+            if k is not None:
+                if recs is None:
+                    raise RuntimeError(f"seq {s.seq_id} asked for logprobs but its step returned none")
+                s.logprobs.append(TokenLogprob(float(recs.logprob[row]), recs.top_ids[row, :k].tolist(),
+                                               recs.top_logprobs[row, :k].tolist()))
             if id(s) in prefill:
                 self.bm.register_computed(s.block_table, s.all_ids[:s.num_computed], s.block_hashes)
                 if s.t_first_token is None:

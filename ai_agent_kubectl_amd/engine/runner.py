@@ -35,6 +35,7 @@ from .sequence import PLACEHOLDER
 
 KIND_STOP, KIND_DECODE, KIND_PREFILL = 0, 1, 2
 HDR = 8
+LP_WORDS = 1 + 2 * ops.MAX_TOP_LOGPROBS   # int32 words per row of a log-probability image at the largest top_n
 
 
 class CollectiveTimeout(RuntimeError):
@@ -68,6 +69,17 @@ class StepHandle(NamedTuple):
     prefill_tokens: int = 0               # > 0: a prefill step (launch_prefill_async)
     progress: Optional["torch.cuda.Event"] = None   # recorded KA_LOOKAHEAD_LAYERS layers before the end
     err_host: Optional[torch.Tensor] = None   # pinned copy of the one-shot collectives' error word
+    lp_host: Optional[torch.Tensor] = None    # pinned [rows, 1 + 2 * lp_n] image of the step's log-probabilities
+    lp_n: int = 0                             # alternatives per row in lp_host
+
+
+class StepLogprobs(NamedTuple):
+    """A step's log-probability records on the host, by batch row (engine._settle takes the rows of
+    the requests that asked)."""
+    logprob: np.ndarray        # fp32 [rows]
+    top_ids: np.ndarray        # int32 [rows, n]
+    top_logprobs: np.ndarray   # fp32 [rows, n]
+
 
 class ModelRunner:
     def __init__(self, cfg: ModelConfig, weights: Dict[str, torch.Tensor], device: torch.device,
@@ -139,6 +151,14 @@ class ModelRunner:
         self.d_samp = torch.zeros(SAMP_WORDS * B, dtype=torch.int32, device=self.device)
         self._h_samps = [torch.zeros(SAMP_WORDS * B, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
         self._mflip = 0
+        # the log-probabilities of a step with a logprobs request ([rows, 1 + 2 * top_n] words per step:
+        # chosen logprob | top ids | top logprobs) come back through pinned images next to the token
+        # outputs, one pair per launch path, one extra async copy behind the tokens.  A step without
+        # such a request never touches them
+        self._h_lps = [torch.zeros(B * LP_WORDS, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
+        self._h_plps = [torch.zeros(B * LP_WORDS, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
+        # the records of the step read back last (collect / execute), for engine._settle to take
+        self.last_logprobs: Optional[StepLogprobs] = None
         self.d_hdr = torch.zeros(HDR, dtype=torch.int32, device=self.device)
         self._h_hdrs = [torch.zeros(HDR, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
         self._hflip = 0
@@ -155,7 +175,8 @@ class ModelRunner:
         self.graphs: Dict[int, torch.cuda.CUDAGraph] = {}
         self.graph_pool = None
         self.stats = {"decode_steps": 0, "prefill_steps": 0, "graph_replays": 0, "decode_ms": 0.0,
-                      "prefill_ms": 0.0, "prefill_tokens": 0, "persistent_stalls": 0, "sampled_steps": 0}
+                      "prefill_ms": 0.0, "prefill_tokens": 0, "persistent_stalls": 0, "sampled_steps": 0,
+                      "logprob_steps": 0}
         # bucket -> the captured graph holds the persistent decode kernel (its error word must be read
         # back on every replay of that graph, whatever model.persistent says now)
         self.graph_persistent: Dict[int, bool] = {}
@@ -182,10 +203,15 @@ class ModelRunner:
         tok = self.model.sample(h, self.mask_bits, mask_idx, samp)
         self.d_out[:B].copy_(tok)
 
-    # ---- seeded sampling: steps that hold a request with temperature > 0 ----
+    # ---- steps that need the logits written: a request with temperature > 0, or with logprobs ----
     @staticmethod
     def _sampling(batch: Batch) -> bool:
         return any(s.params.temperature > 0 for s in batch.seqs)
+
+    @staticmethod
+    def _logprob_n(batch: Batch) -> int:
+        """The largest number of alternatives a request of `batch` asks for; -1: none asks for logprobs."""
+        return max((int(s.params.logprobs) for s in batch.seqs if s.params.logprobs is not None), default=-1)
 
     @staticmethod
     def _pack_samp(seqs, h: np.ndarray, cap: int, ahead: int = 0) -> None:
@@ -206,12 +232,22 @@ class ModelRunner:
 
     def _stage_samp(self, batch: Batch, rows: int, ahead: int = 0) -> Optional[SampleArrays]:
         """The step's sampling arrays on the device (`rows` rows: the batch, then greedy padding), or
-        None when no request of `batch` samples: that step takes the greedy path untouched."""
-        if not self._sampling(batch):
+        None when no request of `batch` samples or asks for logprobs: that step takes the greedy path
+        untouched.  With a logprobs request the arrays carry top_n, and greedy rows go through
+        ops.sample at temperature 0 (the masked argmax, bit for bit)."""
+        top_n = self._logprob_n(batch)
+        if top_n < 0 and not self._sampling(batch):
             return None
         if self.tp_size > 1:
-            raise RuntimeError("sampling with temperature > 0 is not wired through the TP worker protocol")
-        self.stats["sampled_steps"] += 1
+            raise RuntimeError("sampling with temperature > 0 and logprobs are not wired through the TP "
+                               "worker protocol")
+        self.stats["sampled_steps"] += self._sampling(batch)
+        self.stats["logprob_steps"] += top_n >= 0
+        samp = self._stage_samp_arrays(batch, rows, ahead)
+        samp.top_n = top_n
+        return samp
+
+    def _stage_samp_arrays(self, batch: Batch, rows: int, ahead: int) -> SampleArrays:
         if rows > self.bmax:   # a synchronous step larger than the buffers (execute)
             img = np.zeros(SAMP_WORDS * rows, dtype=np.int32)
             self._pack_samp(batch.seqs, img, rows, ahead)
@@ -221,6 +257,36 @@ class ModelRunner:
         self._pack_samp(batch.seqs, hb.numpy(), self.bmax, ahead)
         self.d_samp.copy_(hb, non_blocking=True)
         return SampleArrays.from_image(self.d_samp, self.bmax, rows)
+
+    def _copy_logprobs(self, samp: Optional[SampleArrays], rows: int, bufs: List[torch.Tensor], k: int):
+        """Queue the readback of the step's log-probabilities (the first `rows` rows) behind its tokens:
+        packed on the device into [rows, 1 + 2 * top_n] words, then one async copy into pinned image
+        bufs[k].  -> (image, top_n), or (None, 0) for a step without a logprobs request."""
+        if samp is None or samp.logprobs is None:
+            return None, 0
+        lp, tid, tlp = samp.logprobs
+        n = samp.top_n
+        img = torch.cat([lp[:rows, None].view(torch.int32), tid[:rows], tlp[:rows].view(torch.int32)], dim=1)
+        h = bufs[k][:rows * (1 + 2 * n)].view(rows, 1 + 2 * n)
+        h.copy_(img, non_blocking=True)
+        return h, n
+
+    @staticmethod
+    def _host_logprobs(samp: Optional[SampleArrays], rows: int) -> Optional[StepLogprobs]:
+        """The synchronous path's records, straight from the device tensors."""
+        if samp is None or samp.logprobs is None:
+            return None
+        lp, tid, tlp = (t[:rows].cpu().numpy() for t in samp.logprobs)
+        return StepLogprobs(lp, tid, tlp)
+
+    @staticmethod
+    def _read_logprobs(h: Optional[torch.Tensor], n: int) -> Optional[StepLogprobs]:
+        """A pinned image whose copy has completed -> records (copied out: the image is reused)."""
+        if h is None:
+            return None
+        a = h.numpy()
+        return StepLogprobs(a[:, 0].copy().view(np.float32), a[:, 1:1 + n].copy(),
+                            a[:, 1 + n:1 + 2 * n].copy().view(np.float32))
 
     def _attention_consumer(self, ctx: int = 128):
         """fn(qkv, M): decode_attention_rope over M synthetic sequences of `ctx` cached tokens in
@@ -361,6 +427,7 @@ class ModelRunner:
         samp = self._stage_samp(batch, Bp, ahead=1 if chained else 0)
         self._launch_decode(Bp, n_copy, samp)
         ho[:B].copy_(self.d_out[:B], non_blocking=True)
+        lh, ln = self._copy_logprobs(samp, B, self._h_lps, k)
         # a sampled step ran eagerly beside the bucket's graph: the model's current setting decides
         # whether it launched the persistent kernel, not what the graph was captured with
         eh = self._copy_err(persistent=self._persistent_step(Bp) if samp is None else self.model.persistent_ok(Bp))
@@ -368,7 +435,7 @@ class ModelRunner:
         if self.device.type == "cuda":
             ev = torch.cuda.Event()
             ev.record()
-        return StepHandle(ev, ho, B, t0, err_host=eh)
+        return StepHandle(ev, ho, B, t0, err_host=eh, lp_host=lh, lp_n=ln)
 
     @torch.inference_mode()
     def launch_prefill_async(self, batch: Batch):
@@ -393,21 +460,24 @@ class ModelRunner:
             self.comm.broadcast(buf, src=0)
         self.model.mark_layer = max(0, self.cfg.num_layers - self.lookahead_layers)
         self.model.mark_event = None
+        samp = self._stage_samp(batch, S)
         try:
-            tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens, self._stage_samp(batch, S))
+            tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens, samp)
         finally:
             self.model.mark_layer = -1
         progress, self.model.mark_event = self.model.mark_event, None
         self.d_out[:S].copy_(tok)
-        ho = self._h_pouts[self._pflip]
+        k = self._pflip
+        ho = self._h_pouts[k]
         self._pflip ^= 1
         ho[:S].copy_(tok, non_blocking=True)
+        lh, ln = self._copy_logprobs(samp, S, self._h_plps, k)
         eh = self._copy_err()
         ev = None
         if self.device.type == "cuda":
             ev = torch.cuda.Event()
             ev.record()
-        return StepHandle(ev, ho, S, t0, prefill_tokens=T, progress=progress, err_host=eh)
+        return StepHandle(ev, ho, S, t0, prefill_tokens=T, progress=progress, err_host=eh, lp_host=lh, lp_n=ln)
 
     def _stage_prefill(self, host: np.ndarray) -> torch.Tensor:
         """Packed prefill metadata -> device without a host sync: through one of two pinned buffers
@@ -487,10 +557,14 @@ class ModelRunner:
                                   "the step's results are stale")
 
     def collect(self, handle: "StepHandle") -> List[int]:
+        """Wait for a queued step and return its tokens.  The step's log-probability records (None
+        without a logprobs request) are left in `last_logprobs` for engine._settle."""
         ev, ho, B, t0 = handle.event, handle.host_out, handle.rows, handle.t0
+        self.last_logprobs = None
         if handle.prefill_tokens:   # launch_prefill_async
             if ev is not None:
                 ev.synchronize()
+            self.last_logprobs = self._read_logprobs(handle.lp_host, handle.lp_n)
             now = time.perf_counter()
             self.stats["prefill_steps"] += 1
             self.stats["prefill_tokens"] += handle.prefill_tokens
@@ -501,6 +575,7 @@ class ModelRunner:
         if ev is not None:
             ev.synchronize()
         self._check_err(handle.err_host)
+        self.last_logprobs = self._read_logprobs(handle.lp_host, handle.lp_n)
         now = time.perf_counter()
         # wall time attributed to this step: from its launch (or the previous collect, if later)
         self.stats["decode_ms"] += (now - max(t0, getattr(self, "_last_collect", t0))) * 1e3
@@ -649,6 +724,7 @@ class ModelRunner:
         if B == 0:
             return []
         t0 = time.perf_counter()
+        self.last_logprobs = None
         if batch.is_decode and B <= self.bmax:
             i = bisect.bisect_left(self.buckets, B)
             # pad to the bucket even when running eagerly: identical shapes -> identical GEMM plans
@@ -666,6 +742,7 @@ class ModelRunner:
                 torch.cuda.current_stream(self.device).synchronize()
             self._check_err(eh)
             out = self.h_out[:B].tolist()
+            self.last_logprobs = self._host_logprobs(samp, B)
             self.stats["decode_steps"] += 1
             self.stats["decode_ms"] += (time.perf_counter() - t0) * 1e3
             return out
@@ -676,10 +753,12 @@ class ModelRunner:
         buf = torch.from_numpy(host).to(self.device, non_blocking=False)
         if self.tp_size > 1:
             self.comm.broadcast(buf, src=0)
-        tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens, self._stage_samp(batch, S))
+        samp = self._stage_samp(batch, S)
+        tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens, samp)
         eh = self._copy_err()
         out = tok.cpu().tolist()
         self._check_err(eh)
+        self.last_logprobs = self._host_logprobs(samp, S)
         self.stats["prefill_steps"] += 1
         self.stats["prefill_tokens"] += T
         self.stats["prefill_ms"] += (time.perf_counter() - t0) * 1e3

@@ -6,7 +6,7 @@ import itertools
 import random
 import time
 from dataclasses import dataclass, field
-from typing import Callable, List, Optional
+from typing import Callable, List, NamedTuple, Optional
 
 _ids = itertools.count()
 
@@ -33,6 +33,17 @@ class SamplingParams:
     top_k: int = 0                # 0 = off
     top_p: float = 1.0            # 1 = off
     seed: Optional[int] = None    # None: a random 64-bit seed per sequence (Sequence.sample_seed)
+    # per-token log-probabilities (csrc/logprobs.hip): None = off, 0..20 = the number of alternatives
+    # reported beside every generated token.  They describe the model's distribution under the
+    # SAFE_DECODE mask before temperature / top_k / top_p, so those fields do not change them
+    logprobs: Optional[int] = None
+
+
+class TokenLogprob(NamedTuple):
+    """The record of one model-generated token (Sequence.logprobs)."""
+    logprob: float            # of the chosen token
+    top_ids: List[int]        # the request's `logprobs` most likely tokens, -1 past the allowed count
+    top_logprobs: List[float]
 
 
 @dataclass(eq=False)   # identity semantics: `seq in list` / `remove` must not compare token lists
@@ -57,6 +68,9 @@ class Sequence:
     t_finish: Optional[float] = None
     ph_row: Optional[int] = None            # row of the in-flight step whose token is the PLACEHOLDER
     sample_seed: int = 0                    # the 64 bits the sampling noise is keyed with (params.seed or random)
+    # params.logprobs is set: one TokenLogprob per model-generated token, aligned with `generated`
+    # (the jump-forward prefix has none); appended where the token's placeholder is settled
+    logprobs: List[TokenLogprob] = field(default_factory=list)
 
     def __post_init__(self):
         seed = self.params.seed if self.params.seed is not None else random.getrandbits(64)

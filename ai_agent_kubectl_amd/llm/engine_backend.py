@@ -123,12 +123,45 @@ class EngineLLM(LLMBackend):
         """Returns (text, finish_reason, prompt_tokens, completion_tokens).  temperature 0 (the default)
         decodes greedily; above it the engine samples (top_k / top_p cuts, `seed` makes it repeatable).
         Raises ValueError for a request the engine cannot serve (temperature > 0 under TP > 1)."""
+        seq, n_in = await self._chat(messages, max_tokens, safe, temperature, top_p, top_k, seed, None)
+        out = [t for t in seq.output_ids if not self.tok.is_eos(t)]
+        return self.tok.decode(out), ("stop" if seq.finish_reason == "stop" else "length"), n_in, len(seq.output_ids)
+
+    async def generate_chat_logprobs(self, messages, top_logprobs: int = 0, max_tokens: int = 64, safe: bool = False,
+                                     temperature: float = 0.0, top_p: float = 1.0, top_k: int = 0,
+                                     seed: Optional[int] = None):
+        """generate_chat with per-token log-probabilities: returns its four values and OpenAI's
+        `logprobs.content` list, one {"token", "logprob", "bytes", "top_logprobs": [{"token", "logprob",
+        "bytes"}, ...]} per model-generated token that makes up the text (the stripped EOS and a
+        jump-forward prefix have none), with `top_logprobs` (0..20) alternatives each.  The values are
+        the model's distribution under the token mask before temperature / top_k / top_p (ops.token_logprobs).
+        Raises ValueError under TP > 1."""
+        seq, n_in = await self._chat(messages, max_tokens, safe, temperature, top_p, top_k, seed, int(top_logprobs))
+        tok = self.tok
+        out = [t for t in seq.output_ids if not tok.is_eos(t)]
+
+        def entry(tid: int, lp: float) -> dict:
+            return {"token": tok.decode([tid]), "logprob": lp, "bytes": list(tok.token_bytes(tid))}
+
+        content = []
+        for tid, rec in zip(seq.generated, seq.logprobs):
+            if tok.is_eos(tid):
+                continue
+            e = entry(tid, rec.logprob)
+            e["top_logprobs"] = [entry(i, l) for i, l in zip(rec.top_ids, rec.top_logprobs) if i >= 0]
+            content.append(e)
+        return (tok.decode(out), ("stop" if seq.finish_reason == "stop" else "length"), n_in, len(seq.output_ids),
+                content)
+
+    async def _chat(self, messages, max_tokens, safe, temperature, top_p, top_k, seed, logprobs):
+        """Submit one chat request and wait for it -> (finished sequence, prompt tokens)."""
         if not self._started:
             await self.start()
         loop = asyncio.get_running_loop()
         fut: asyncio.Future = loop.create_future()
         params = SamplingParams(max_new_tokens=max_tokens, ignore_eos=False, safe_decode=safe,
-                                temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=seed)
+                                temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=seed,
+                                logprobs=logprobs)
         ids = self.chat_ids(messages)
         seq = self.engine.submit(ids, params, lambda sq: loop.call_soon_threadsafe(_resolve, fut, sq),
                                  forced_prefix=self._forced if safe else None)
@@ -139,8 +172,7 @@ class EngineLLM(LLMBackend):
             raise
         if seq.error is not None:
             raise LLMUnavailableError(str(seq.error))
-        out = [t for t in seq.output_ids if not self.tok.is_eos(t)]
-        return self.tok.decode(out), ("stop" if seq.finish_reason == "stop" else "length"), len(ids), len(seq.output_ids)
+        return seq, len(ids)
 
 
 def _resolve(fut: asyncio.Future, seq) -> None:

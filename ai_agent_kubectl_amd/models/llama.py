@@ -63,6 +63,8 @@ class SampleArrays:
     top_p: torch.Tensor                # fp32, 1 = off
     seed: torch.Tensor                 # int64 (the 64 seed bits)
     position: torch.Tensor             # int32: tokens generated so far (the count that picks the mask row)
+    top_n: int = -1                    # >= 0: also report log-probabilities, with this many alternatives per row
+    logprobs: Optional[tuple] = None   # set by LlamaModel.sample when top_n >= 0: (lp [S], top_id, top_lp [S, top_n])
 
     @classmethod
     def from_image(cls, img: torch.Tensor, cap: int, n: int) -> "SampleArrays":
@@ -333,12 +335,18 @@ class LlamaModel:
         one kernel and the logits are never written.
         samp: the per-row sampling arrays of a step with at least one temperature > 0 request (TP = 1):
         the logits are then written (unfused LM head) and every row goes through ops.sample, the
-        greedy requests' rows at temperature 0."""
+        greedy requests' rows at temperature 0.  A step with a logprobs request takes the same route
+        (samp.top_n >= 0): ops.token_logprobs then reads the sampled tokens on the device, over all rows
+        of the step, and leaves its outputs in samp.logprobs."""
         if samp is not None:
             if self.tp_size != 1:
                 raise RuntimeError("sampling with temperature > 0 is not wired through the TP worker protocol")
-            idx, _ = ops.sample(self.logits(hidden_last), mask_bits, mask_idx, samp.temperature, samp.top_k,
+            logits = self.logits(hidden_last)
+            idx, _ = ops.sample(logits, mask_bits, mask_idx, samp.temperature, samp.top_k,
                                 samp.top_p, samp.seed, samp.position, vocab_offset=self.vocab_offset)
+            if samp.top_n >= 0:
+                samp.logprobs = ops.token_logprobs(logits, mask_bits, mask_idx, idx, samp.top_n,
+                                                   vocab_offset=self.vocab_offset)
             return idx
         lm = self.W["lm_head"]
         if ops.use_fused_lm_head(hidden_last, lm, self.vocab_offset):

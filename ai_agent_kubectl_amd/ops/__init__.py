@@ -335,6 +335,50 @@ def sample(logits: torch.Tensor, mask_bits: Optional[torch.Tensor], mask_idx: Op
     return (out_idx, out_val, cut, kept) if return_cut else (out_idx, out_val)
 
 
+MAX_TOP_LOGPROBS = 20
+
+
+def token_logprobs(logits: torch.Tensor, mask_bits: Optional[torch.Tensor], mask_idx: Optional[torch.Tensor],
+                   token: torch.Tensor, top_n: int, vocab_offset: int = 0, return_probe: bool = False):
+    """Log-probability of `token[r]` (int32 global ids, read on the device: the sampler's output) and the
+    `top_n` (0..20) most likely tokens per row among the tokens mask row `mask_idx[r]` allows
+    (csrc/logprobs.hip; semantics: ops/reference.py `token_logprobs`).  The distribution is the model's
+    own under the SAFE_DECODE mask, before temperature / top-k / top-p / seed: what a request samples
+    with does not change what is reported.  The top list is ordered by (logit descending, global id
+    ascending), so the top-n list is a prefix of the top-20 list; entries past the allowed count are id
+    -1, -inf; a token outside the mask or the slice [vocab_offset, vocab_offset + V) gets -inf.
+    -> (lp fp32 [R], top_id int32 [R, top_n], top_lp fp32 [R, top_n])
+       [+ (max fp32, count int32, mass int64) [R] with return_probe: the largest allowed logit, the
+       allowed count and the u64 fixed-point mass sum trunc(exp(l - max) * 2^40)]."""
+    top_n = int(top_n)
+    if not 0 <= top_n <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"token_logprobs: top_n must be in 0..{MAX_TOP_LOGPROBS}")
+    if _ref(logits):
+        return ref.token_logprobs(logits, mask_bits, mask_idx, token, top_n, vocab_offset, return_probe=return_probe)
+    lib = require()
+    B, V = logits.shape
+    dev = logits.device
+    if token is None or token.dtype != torch.int32 or token.shape != (B,) or token.device != dev \
+            or not token.is_contiguous():
+        raise ValueError(f"token_logprobs: token must be a contiguous {torch.int32} [{B}] tensor on {dev}")
+    if not logits.is_contiguous() or logits.dtype != torch.bfloat16:
+        raise ValueError("token_logprobs: logits must be contiguous bf16 [rows, vocab]")
+    lp = torch.empty(B, dtype=torch.float32, device=dev)
+    top_id = torch.empty((B, top_n), dtype=torch.int32, device=dev)
+    top_lp = torch.empty((B, top_n), dtype=torch.float32, device=dev)
+    mx = torch.empty(B, dtype=torch.float32, device=dev) if return_probe else None
+    cnt = torch.empty(B, dtype=torch.int32, device=dev) if return_probe else None
+    mass = torch.empty(B, dtype=torch.int64, device=dev) if return_probe else None
+    words = mask_bits.shape[1] if mask_bits is not None else 0
+    slices = lib.ka_argmax_slices(B, V)   # small batches: the row is split over workgroups
+    ws = torch.empty(max(1, lib.ka_token_logprobs_ws_words(B, slices, top_n)), dtype=torch.int32, device=dev)
+    check(lib.ka_token_logprobs(_p(lp), _p(top_id) if top_n else None, _p(top_lp) if top_n else None, _p(mx), _p(cnt),
+                                _p(mass), _p(logits), _p(mask_bits), _p(mask_idx) if mask_bits is not None else None,
+                                _p(token), top_n, B, V, words, int(vocab_offset), _p(ws), slices, _stream()),
+          "token_logprobs")
+    return (lp, top_id, top_lp, mx, cnt, mass) if return_probe else (lp, top_id, top_lp)
+
+
 def argmax_combine(vals: torch.Tensor, idxs: torch.Tensor) -> torch.Tensor:
     """TP vocab-parallel greedy combine: vals / idxs [ranks, S] (every rank's best value and global token
     id) -> [S] int32 id of the largest value, the lowest id on ties (csrc/sampling.hip)."""

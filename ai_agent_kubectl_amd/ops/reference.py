@@ -255,3 +255,62 @@ def sample(logits, mask_bits, mask_idx, temperature, top_k, top_p, seed, positio
     if return_margins:
         out += (gap, p_lo, p_hi)
     return out
+
+
+# ---- per-token log-probabilities (csrc/logprobs.hip) ----
+def token_logprobs(logits, mask_bits, mask_idx, token, top_n: int, vocab_offset: int = 0,
+                   return_probe: bool = False, dtype=torch.float32):
+    """Log-probability of `token[r]` (global id) and the `top_n` most likely tokens per row among the
+    tokens mask row `mask_idx[r]` allows (-1 = all), A:
+        m = max over A of l;  w = exp(l - m);  mass = sum over A of trunc(w * 2^40) (an integer);
+        S = mass * 2^-40;  logprob(i) = (l_i - m) - log(S), -inf outside A or outside the vocab slice.
+    This is the model's distribution under the mask BEFORE temperature / top-k / top-p / seed, which
+    shape the draw only.  A weight below 2^-40 counts as zero.  The top list is ordered by (exact bf16
+    value descending, global id ascending): a prefix of the top-20 list; entries past |A| are id -1,
+    -inf.  dtype: of the weights, the logarithm and the subtractions (float64: ground truth).
+    -> (lp [R], top_id int32 [R, top_n], top_lp [R, top_n]) [+ (max fp32, count int32, mass int64) with
+    return_probe]; lp and top_lp in `dtype`."""
+    R, V = logits.shape
+    dev = logits.device
+    lp = torch.full((R,), float("-inf"), dtype=dtype, device=dev)
+    top_id = torch.full((R, top_n), -1, dtype=torch.int32, device=dev)
+    top_lp = torch.full((R, top_n), float("-inf"), dtype=dtype, device=dev)
+    mx = torch.full((R,), float("-inf"), dtype=torch.float32, device=dev)
+    cnt = torch.zeros(R, dtype=torch.int32, device=dev)
+    mass = torch.zeros(R, dtype=torch.int64, device=dev)
+    gid = torch.arange(V, device=dev) + vocab_offset
+    masked = mask_bits is not None and mask_idx is not None
+    if masked:
+        words = mask_bits[:, gid // 32].long()
+        allowed_rows = ((words >> (gid % 32)) & 1).bool()
+    toks = token.cpu().tolist()
+    for r in range(R):
+        mi = int(mask_idx[r]) if masked else -1
+        allowed = allowed_rows[mi] if mi >= 0 else torch.ones(V, dtype=torch.bool, device=dev)
+        ids = allowed.nonzero().squeeze(1)
+        cnt[r] = ids.numel()
+        if ids.numel() == 0:
+            continue
+        la = logits[r].float()[ids]
+        m = la.max()
+        mx[r] = m + 0.0   # -0 counts as +0
+        d = la.to(dtype) - m.to(dtype)
+        wi = torch.trunc(torch.exp(d) * 2.0 ** 40).to(torch.int64)
+        mass[r] = wi.sum()
+        log_s = torch.log(mass[r].to(dtype) * 2.0 ** -40)
+        all_lp = d - log_s
+        i = toks[r] - vocab_offset
+        if 0 <= i < V and bool(allowed[i]):
+            lp[r] = (logits[r, i].float().to(dtype) - m.to(dtype)) - log_s
+        if top_n:
+            # everything at or above the n-th largest value, in id order, then a stable sort by value:
+            # ties keep the lowest id first
+            pool = (la >= torch.topk(la, min(top_n, la.numel())).values[-1]).nonzero().squeeze(1)
+            order = pool[torch.sort(la[pool], descending=True, stable=True).indices[:top_n]]
+            n = order.numel()
+            top_id[r, :n] = (ids[order] + vocab_offset).to(torch.int32)
+            top_lp[r, :n] = all_lp[order]
+    out = (lp, top_id, top_lp)
+    if return_probe:
+        out += (mx, cnt, mass)
+    return out

@@ -5,7 +5,7 @@
 
 Each csrc/*.hip (default: all; a file is named by its basename or any path to it) is compiled to device
 assembly with build.py's flags, once from `git show REV:...` and once from the working tree, each next
-to its own csrc/common.h.  Lines carrying the `__hip_cuid_<hash>` symbol (a hash of the source text) are
+to its own csrc/*.h.  Lines carrying the `__hip_cuid_<hash>` symbol (a hash of the source text) are
 dropped; the listing has no line information, so a clean-up that changes no instruction compares equal.
 Prints one `identical` / `DIFFERENT` line per file; exits 1 on any difference.  Needs no GPU.
 """
@@ -41,10 +41,15 @@ def main(argv):
     with tempfile.TemporaryDirectory() as tmp:
         old, new = os.path.join(tmp, "old"), os.path.join(tmp, "new")
         os.mkdir(old), os.mkdir(new)
-        for name in names + ["common.h"]:
-            with open(os.path.join(old, name), "wb") as f:
-                f.write(subprocess.run(["git", "-C", ROOT, "show", f"{rev}:{REL}/{name}"], check=True,
-                                       stdout=subprocess.PIPE).stdout)
+        headers = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.h")))
+        for name in names + headers:
+            r = subprocess.run(["git", "-C", ROOT, "show", f"{rev}:{REL}/{name}"], stdout=subprocess.PIPE,
+                               stderr=subprocess.DEVNULL)
+            if r.returncode == 0:
+                with open(os.path.join(old, name), "wb") as f:
+                    f.write(r.stdout)
+            elif not name.endswith(".h"):   # a header may be newer than REV; a kernel file must exist there
+                raise RuntimeError(f"{name} does not exist at {rev}")
             with open(os.path.join(CSRC, name), "rb") as g, open(os.path.join(new, name), "wb") as f:
                 f.write(g.read())
         with cf.ThreadPoolExecutor(16) as ex:   # at most 16 compiles at a time
