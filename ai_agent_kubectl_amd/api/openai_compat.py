@@ -14,16 +14,20 @@ content, each with `top_logprobs` (0..20) alternatives (csrc/logprobs.hip).  The
 distribution under the token mask BEFORE temperature / top_p / top_k are applied (what vLLM reports by
 default), so they do not depend on those fields or on `seed`.  `top_logprobs` without `logprobs: true`
 gets 422; logprobs on a tensor-parallel engine get 400.
+`presence_penalty`, `frequency_penalty` (-2..2), `repetition_penalty` (0 < r <= 2, the vLLM / HF extension) and
+`logit_bias` ({"<token id>": -100..100}, at most 300 entries) edit the logits before the token is chosen, also
+at temperature 0 (csrc/logit_adjust.hip); `logprobs` stay the model's raw ones.  Out-of-range values and
+non-integer keys get 422; a token id past the vocabulary and any of the four on a tensor-parallel engine get 400.
 Auth: when API_AUTH_KEY is set, `Authorization: Bearer <key>` or `X-API-Key: <key>`.
 """
 from __future__ import annotations
 
 import time
 import uuid
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 from fastapi import Header, HTTPException, Request
-from pydantic import BaseModel, Field, model_validator
+from pydantic import BaseModel, Field, field_validator, model_validator
 
 
 class ChatMessage(BaseModel):
@@ -42,12 +46,33 @@ class ChatRequest(BaseModel):
     stream: Optional[bool] = False
     logprobs: Optional[bool] = False
     top_logprobs: Optional[int] = Field(None, ge=0, le=20)
+    presence_penalty: Optional[float] = Field(0.0, ge=-2.0, le=2.0)
+    frequency_penalty: Optional[float] = Field(0.0, ge=-2.0, le=2.0)
+    repetition_penalty: Optional[float] = Field(1.0, gt=0.0, le=2.0)
+    logit_bias: Optional[Dict[str, float]] = None   # OpenAI's wire form: decimal token-id strings -> bias
+
+    @field_validator("logit_bias")
+    @classmethod
+    def _logit_bias_entries(cls, v):
+        if v is None:
+            return v
+        if len(v) > 300:
+            raise ValueError("logit_bias accepts at most 300 entries")
+        for key, b in v.items():
+            if not (key.isascii() and key.isdigit()):
+                raise ValueError(f"logit_bias key {key!r} is not a token id")
+            if not -100.0 <= b <= 100.0:
+                raise ValueError(f"logit_bias value for token {key} must be in -100..100")
+        return v
 
     @model_validator(mode="after")
     def _top_logprobs_needs_logprobs(self):
         if self.top_logprobs is not None and not self.logprobs:
             raise ValueError("top_logprobs requires logprobs: true")
         return self
+
+
+_NEUTRAL = dict(presence_penalty=0.0, frequency_penalty=0.0, repetition_penalty=1.0, logit_bias=None)
 
 
 def install(app, svc, settings) -> None:
@@ -77,6 +102,12 @@ def install(app, svc, settings) -> None:
         msgs = [m.model_dump() for m in req.messages]
         kw = dict(max_tokens=req.max_tokens or 64, temperature=req.temperature or 0.0,
                   top_p=1.0 if req.top_p is None else req.top_p, top_k=req.top_k or 0, seed=req.seed)
+        bias = {int(t): b for t, b in (req.logit_bias or {}).items()}
+        pen = dict(presence_penalty=req.presence_penalty or 0.0, frequency_penalty=req.frequency_penalty or 0.0,
+                   repetition_penalty=1.0 if req.repetition_penalty is None else req.repetition_penalty,
+                   logit_bias=bias or None)
+        if pen != _NEUTRAL:   # only when sent: a plain request is submitted exactly as it always was
+            kw.update(pen)
         content = None
         try:
             if req.logprobs:
@@ -86,7 +117,7 @@ def install(app, svc, settings) -> None:
                     msgs, top_logprobs=req.top_logprobs or 0, **kw)
             else:
                 text, finish, n_in, n_out = await backend.generate_chat(msgs, **kw)
-        except ValueError as e:   # a request this engine cannot serve (temperature > 0 / logprobs under TP > 1)
+        except ValueError as e:   # a request this engine cannot serve (sampling / logprobs / penalties under TP > 1)
             raise HTTPException(status_code=400, detail=str(e))
         choice = {"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": finish}
         if content is not None:   # only when asked for: the response is otherwise what it always was

@@ -31,6 +31,7 @@ import threading
 import time
 from typing import Callable, Dict, List, Optional
 
+from . import penalties
 from .block_manager import make_block_manager
 from .runner import CollectiveTimeout, ModelRunner
 from .scheduler import Scheduler
@@ -168,6 +169,7 @@ class LLMEngine:
             if self.runner.tp_size > 1:
                 # the logits are vocab-parallel: the ranks' (max, mass) pairs would have to be combined
                 raise ValueError("logprobs are not supported with tensor parallelism (TP > 1)")
+        penalties.validate(params, self.runner.cfg.vocab_size, self.runner.tp_size)
         seq = Sequence(prompt_ids=list(prompt_ids), params=params, callback=callback,
                        forced_prefix=list(forced_prefix or []))
         self._inbox.put(("add", seq))

@@ -24,11 +24,12 @@ import torch
 
 from ..models.config import ModelConfig
 from .. import ops
-from ..models.llama import SAMP_WORDS, AttnMeta, LlamaModel, SampleArrays
+from ..models.llama import SAMP_WORDS, AttnMeta, LlamaModel, LogitEdits, SampleArrays
 from ..ops.autotune import tune_engine
 
 logger = logging.getLogger("app.engine")
 from ..parallel.comm import LocalComm
+from .penalties import pack_edits
 from .safe_decode import mask_index_for
 from .scheduler import Batch
 from .sequence import PLACEHOLDER
@@ -157,6 +158,10 @@ class ModelRunner:
         # such a request never touches them
         self._h_lps = [torch.zeros(B * LP_WORDS, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
         self._h_plps = [torch.zeros(B * LP_WORDS, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
+        # the penalty / logit_bias image of a step with such a request (models/llama.py LogitEdits):
+        # pinned and double-buffered like the prefill metadata, grown on demand (_stage_edits)
+        self._h_pen: List[Optional[torch.Tensor]] = [None, None]
+        self._nflip = 0
         # the records of the step read back last (collect / execute), for engine._settle to take
         self.last_logprobs: Optional[StepLogprobs] = None
         self.d_hdr = torch.zeros(HDR, dtype=torch.int32, device=self.device)
@@ -176,7 +181,7 @@ class ModelRunner:
         self.graph_pool = None
         self.stats = {"decode_steps": 0, "prefill_steps": 0, "graph_replays": 0, "decode_ms": 0.0,
                       "prefill_ms": 0.0, "prefill_tokens": 0, "persistent_stalls": 0, "sampled_steps": 0,
-                      "logprob_steps": 0}
+                      "logprob_steps": 0, "penalty_steps": 0}
         # bucket -> the captured graph holds the persistent decode kernel (its error word must be read
         # back on every replay of that graph, whatever model.persistent says now)
         self.graph_persistent: Dict[int, bool] = {}
@@ -203,7 +208,8 @@ class ModelRunner:
         tok = self.model.sample(h, self.mask_bits, mask_idx, samp)
         self.d_out[:B].copy_(tok)
 
-    # ---- steps that need the logits written: a request with temperature > 0, or with logprobs ----
+    # ---- steps that need the logits written: a request with temperature > 0, with logprobs, or with
+    # penalties / logit_bias ----
     @staticmethod
     def _sampling(batch: Batch) -> bool:
         return any(s.params.temperature > 0 for s in batch.seqs)
@@ -230,22 +236,46 @@ class ModelRunner:
             h[3 * cap + i] = s.num_generated + ahead
             sd[i] = s.sample_seed
 
-    def _stage_samp(self, batch: Batch, rows: int, ahead: int = 0) -> Optional[SampleArrays]:
+    def _stage_samp(self, batch: Batch, rows: int, ahead: int = 0,
+                    pend: Optional[List[int]] = None) -> Optional[SampleArrays]:
         """The step's sampling arrays on the device (`rows` rows: the batch, then greedy padding), or
-        None when no request of `batch` samples or asks for logprobs: that step takes the greedy path
-        untouched.  With a logprobs request the arrays carry top_n, and greedy rows go through
-        ops.sample at temperature 0 (the masked argmax, bit for bit)."""
+        None when no request of `batch` samples, asks for logprobs or carries penalties / logit_bias:
+        that step takes the greedy path untouched.  With a logprobs request the arrays carry top_n, with
+        a penalised one the edit image (`pend`: per batch row the d_out slot of its newest token when
+        that is still on the device, else -1), and greedy rows go through ops.sample at temperature 0
+        (the masked argmax, bit for bit)."""
         top_n = self._logprob_n(batch)
-        if top_n < 0 and not self._sampling(batch):
+        penalised = any(s.params.penalised for s in batch.seqs)
+        if top_n < 0 and not penalised and not self._sampling(batch):
             return None
         if self.tp_size > 1:
-            raise RuntimeError("sampling with temperature > 0 and logprobs are not wired through the TP "
-                               "worker protocol")
+            raise RuntimeError("sampling with temperature > 0, logprobs and penalties are not wired through "
+                               "the TP worker protocol")
         self.stats["sampled_steps"] += self._sampling(batch)
         self.stats["logprob_steps"] += top_n >= 0
+        self.stats["penalty_steps"] += penalised
         samp = self._stage_samp_arrays(batch, rows, ahead)
         samp.top_n = top_n
+        if penalised:
+            samp.edits = self._stage_edits(batch, rows, pend)
         return samp
+
+    def _stage_edits(self, batch: Batch, rows: int, pend: Optional[List[int]]) -> LogitEdits:
+        """The step's penalty / logit_bias image (engine/penalties.py pack_edits) -> device without a host
+        sync: through one of two pinned buffers, grown on demand (the one refilled here served the
+        launch before last, already read back).  The pending tokens are read from d_out on the device."""
+        img, E = pack_edits(batch.seqs, rows, pend)
+        if self.device.type != "cuda":
+            return LogitEdits.from_image(torch.from_numpy(img), rows, E, self.d_out)
+        n = img.shape[0]
+        k = self._nflip = self._nflip ^ 1
+        hb = self._h_pen[k]
+        if hb is None or hb.numel() < n:
+            hb = torch.empty(max(n, 2 * (hb.numel() if hb is not None else 0), 1 << 14), dtype=torch.int32,
+                             pin_memory=True)
+            self._h_pen[k] = hb
+        hb.numpy()[:n] = img
+        return LogitEdits.from_image(hb[:n].to(self.device, non_blocking=True), rows, E, self.d_out)
 
     def _stage_samp_arrays(self, batch: Batch, rows: int, ahead: int) -> SampleArrays:
         if rows > self.bmax:   # a synchronous step larger than the buffers (execute)
@@ -424,7 +454,16 @@ class ModelRunner:
             o = self._off["ids"]
             self.d_stage[o:o + Bp].index_copy_(0, self.d_fix[:nf].long(),
                                                self.d_out.index_select(0, self.d_fix[nf:2 * nf].long()))
-        samp = self._stage_samp(batch, Bp, ahead=1 if chained else 0)
+        # rows whose newest output token is still in d_out (not in output_ids, or there as a PLACEHOLDER):
+        # what a penalised row's counts are still missing
+        pend = None
+        if chained:
+            pend = list(range(B))
+        elif fix:
+            pend = [-1] * B
+            for row, src in fix:
+                pend[row] = src
+        samp = self._stage_samp(batch, Bp, ahead=1 if chained else 0, pend=pend)
         self._launch_decode(Bp, n_copy, samp)
         ho[:B].copy_(self.d_out[:B], non_blocking=True)
         lh, ln = self._copy_logprobs(samp, B, self._h_lps, k)
@@ -460,7 +499,10 @@ class ModelRunner:
             self.comm.broadcast(buf, src=0)
         self.model.mark_layer = max(0, self.cfg.num_layers - self.lookahead_layers)
         self.model.mark_event = None
-        samp = self._stage_samp(batch, S)
+        # the decode rows of a mixed step scheduled ahead: the same rows _pack_prefill fixed up
+        pend = [s.ph_row if s.ph_row is not None and s.num_computed + nq == s.total_len else -1
+                for s, nq in zip(batch.seqs, batch.num_query)] if nf else None
+        samp = self._stage_samp(batch, S, pend=pend)
         try:
             tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens, samp)
         finally:

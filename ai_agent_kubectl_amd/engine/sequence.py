@@ -6,7 +6,7 @@ import itertools
 import random
 import time
 from dataclasses import dataclass, field
-from typing import Callable, List, NamedTuple, Optional
+from typing import Callable, Dict, List, NamedTuple, Optional
 
 _ids = itertools.count()
 
@@ -37,6 +37,18 @@ class SamplingParams:
     # reported beside every generated token.  They describe the model's distribution under the
     # SAFE_DECODE mask before temperature / top_k / top_p, so those fields do not change them
     logprobs: Optional[int] = None
+    # edits of the logits before the sampler reads them (csrc/logit_adjust.hip; ops/reference.py
+    # `logit_adjust` defines them), also at temperature 0.  c = a token's occurrences in the output so far
+    presence_penalty: float = 0.0     # -2..2: subtracted once from every token with c > 0
+    frequency_penalty: float = 0.0    # -2..2: times c, subtracted
+    repetition_penalty: float = 1.0   # 0 < r <= 2 (vLLM / HF): a token of the prompt or the output: l / r if l > 0 else l * r
+    logit_bias: Optional[Dict[int, float]] = None   # token id -> -100..100, at most 300 entries; added last
+
+    @property
+    def penalised(self) -> bool:
+        """Any of the four fields is not neutral: the request's steps take the penalty route."""
+        return (self.presence_penalty != 0 or self.frequency_penalty != 0 or self.repetition_penalty != 1
+                or bool(self.logit_bias))
 
 
 class TokenLogprob(NamedTuple):
@@ -71,6 +83,8 @@ class Sequence:
     # params.logprobs is set: one TokenLogprob per model-generated token, aligned with `generated`
     # (the jump-forward prefix has none); appended where the token's placeholder is settled
     logprobs: List[TokenLogprob] = field(default_factory=list)
+    # params.penalised: the per-sequence part of the penalty image (engine/penalties.py PenaltyState)
+    penalty_state: Optional[object] = None
 
     def __post_init__(self):
         seed = self.params.seed if self.params.seed is not None else random.getrandbits(64)

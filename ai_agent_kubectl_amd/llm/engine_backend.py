@@ -119,24 +119,29 @@ class EngineLLM(LLMBackend):
         return [tok.bos_id] + tok.encode(text)
 
     async def generate_chat(self, messages, max_tokens: int = 64, safe: bool = False, temperature: float = 0.0,
-                            top_p: float = 1.0, top_k: int = 0, seed: Optional[int] = None):
+                            top_p: float = 1.0, top_k: int = 0, seed: Optional[int] = None, **penalties):
         """Returns (text, finish_reason, prompt_tokens, completion_tokens).  temperature 0 (the default)
         decodes greedily; above it the engine samples (top_k / top_p cuts, `seed` makes it repeatable).
-        Raises ValueError for a request the engine cannot serve (temperature > 0 under TP > 1)."""
-        seq, n_in = await self._chat(messages, max_tokens, safe, temperature, top_p, top_k, seed, None)
+        penalties: presence_penalty, frequency_penalty, repetition_penalty, logit_bias ({token id: bias}),
+        applied to the logits before the token is chosen, also at temperature 0 (SamplingParams).
+        Raises ValueError for a request the engine cannot serve (temperature > 0 or penalties under
+        TP > 1, a logit_bias id outside the vocabulary)."""
+        seq, n_in = await self._chat(messages, max_tokens, safe, temperature, top_p, top_k, seed, None, **penalties)
         out = [t for t in seq.output_ids if not self.tok.is_eos(t)]
         return self.tok.decode(out), ("stop" if seq.finish_reason == "stop" else "length"), n_in, len(seq.output_ids)
 
     async def generate_chat_logprobs(self, messages, top_logprobs: int = 0, max_tokens: int = 64, safe: bool = False,
                                      temperature: float = 0.0, top_p: float = 1.0, top_k: int = 0,
-                                     seed: Optional[int] = None):
+                                     seed: Optional[int] = None, **penalties):
         """generate_chat with per-token log-probabilities: returns its four values and OpenAI's
         `logprobs.content` list, one {"token", "logprob", "bytes", "top_logprobs": [{"token", "logprob",
         "bytes"}, ...]} per model-generated token that makes up the text (the stripped EOS and a
         jump-forward prefix have none), with `top_logprobs` (0..20) alternatives each.  The values are
-        the model's distribution under the token mask before temperature / top_k / top_p (ops.token_logprobs).
+        the model's distribution under the token mask before temperature / top_k / top_p and before the
+        penalties and logit_bias (ops.token_logprobs): a token's logprob is its raw one.
         Raises ValueError under TP > 1."""
-        seq, n_in = await self._chat(messages, max_tokens, safe, temperature, top_p, top_k, seed, int(top_logprobs))
+        seq, n_in = await self._chat(messages, max_tokens, safe, temperature, top_p, top_k, seed, int(top_logprobs),
+                                     **penalties)
         tok = self.tok
         out = [t for t in seq.output_ids if not tok.is_eos(t)]
 
@@ -153,7 +158,9 @@ class EngineLLM(LLMBackend):
         return (tok.decode(out), ("stop" if seq.finish_reason == "stop" else "length"), n_in, len(seq.output_ids),
                 content)
 
-    async def _chat(self, messages, max_tokens, safe, temperature, top_p, top_k, seed, logprobs):
+    async def _chat(self, messages, max_tokens, safe, temperature, top_p, top_k, seed, logprobs,
+                    presence_penalty: float = 0.0, frequency_penalty: float = 0.0, repetition_penalty: float = 1.0,
+                    logit_bias=None):
         """Submit one chat request and wait for it -> (finished sequence, prompt tokens)."""
         if not self._started:
             await self.start()
@@ -161,7 +168,10 @@ class EngineLLM(LLMBackend):
         fut: asyncio.Future = loop.create_future()
         params = SamplingParams(max_new_tokens=max_tokens, ignore_eos=False, safe_decode=safe,
                                 temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=seed,
-                                logprobs=logprobs)
+                                logprobs=logprobs, presence_penalty=float(presence_penalty),
+                                frequency_penalty=float(frequency_penalty),
+                                repetition_penalty=float(repetition_penalty),
+                                logit_bias={int(t): float(b) for t, b in logit_bias.items()} if logit_bias else None)
         ids = self.chat_ids(messages)
         seq = self.engine.submit(ids, params, lambda sq: loop.call_soon_threadsafe(_resolve, fut, sq),
                                  forced_prefix=self._forced if safe else None)

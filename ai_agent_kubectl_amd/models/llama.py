@@ -56,6 +56,38 @@ SAMP_WORDS = 6   # int32 words per row of a packed sampling image
 
 
 @dataclass
+class LogitEdits:
+    """The penalty / logit_bias image of a step (ops.logit_adjust), on the logits' device: CSR entries
+    per row and the row's parameters; rows of requests without such fields have empty segments and
+    neutral parameters."""
+    row_start: torch.Tensor            # int32 [S + 1]
+    ent_id: torch.Tensor               # int32 [E] global token ids, distinct within a row
+    ent_cnt: torch.Tensor              # int32 [E] bits 0-30: occurrences in the output; bit 31: occurs in the prompt
+    ent_bias: torch.Tensor             # fp32 [E]
+    presence: torch.Tensor             # fp32 [S]
+    frequency: torch.Tensor            # fp32 [S]
+    repetition: torch.Tensor           # fp32 [S]
+    pend_src: torch.Tensor             # int32 [S]: >= 0: the row's newest output token is tokens[pend_src], uncounted
+    tokens: torch.Tensor               # int32: the runner's d_out
+
+    @classmethod
+    def from_image(cls, img: torch.Tensor, rows: int, entries: int, tokens: torch.Tensor) -> "LogitEdits":
+        """Views of a packed int32 image [row_start (rows + 1) | presence | frequency | repetition | pend_src
+        (rows each) | ids | cnts | biases (entries each)]."""
+        o = rows + 1
+        par = [img[o + i * rows:o + (i + 1) * rows] for i in range(4)]
+        o += 4 * rows
+        ent = [img[o + i * entries:o + (i + 1) * entries] for i in range(3)]
+        return cls(row_start=img[:rows + 1], ent_id=ent[0], ent_cnt=ent[1], ent_bias=ent[2].view(torch.float32),
+                   presence=par[0].view(torch.float32), frequency=par[1].view(torch.float32),
+                   repetition=par[2].view(torch.float32), pend_src=par[3], tokens=tokens)
+
+    @staticmethod
+    def image_words(rows: int, entries: int) -> int:
+        return 5 * rows + 1 + 3 * entries
+
+
+@dataclass
 class SampleArrays:
     """Per-row sampling arrays of a step (ops.sample), [S] each on the logits' device."""
     temperature: torch.Tensor          # fp32, 0 = greedy
@@ -65,6 +97,7 @@ class SampleArrays:
     position: torch.Tensor             # int32: tokens generated so far (the count that picks the mask row)
     top_n: int = -1                    # >= 0: also report log-probabilities, with this many alternatives per row
     logprobs: Optional[tuple] = None   # set by LlamaModel.sample when top_n >= 0: (lp [S], top_id, top_lp [S, top_n])
+    edits: Optional[LogitEdits] = None   # a step with a penalty / logit_bias request: applied before the sampler
 
     @classmethod
     def from_image(cls, img: torch.Tensor, cap: int, n: int) -> "SampleArrays":
@@ -337,14 +370,25 @@ class LlamaModel:
         the logits are then written (unfused LM head) and every row goes through ops.sample, the
         greedy requests' rows at temperature 0.  A step with a logprobs request takes the same route
         (samp.top_n >= 0): ops.token_logprobs then reads the sampled tokens on the device, over all rows
-        of the step, and leaves its outputs in samp.logprobs."""
+        of the step, and leaves its outputs in samp.logprobs.  A step with a penalty / logit_bias request
+        (samp.edits) also takes this route: ops.logit_adjust edits the written logits before the sampler
+        reads them (the mask still wins: a forbidden token stays forbidden whatever its bias), and
+        ops.logit_restore puts the model's own logits back before the log-probabilities are taken."""
         if samp is not None:
             if self.tp_size != 1:
                 raise RuntimeError("sampling with temperature > 0 is not wired through the TP worker protocol")
             logits = self.logits(hidden_last)
+            ed, saved = samp.edits, None
+            if ed is not None:
+                saved = ops.logit_adjust(logits, ed.row_start, ed.ent_id, ed.ent_cnt, ed.ent_bias, ed.presence,
+                                         ed.frequency, ed.repetition, ed.pend_src, ed.tokens,
+                                         vocab_offset=self.vocab_offset, save=samp.top_n >= 0)
             idx, _ = ops.sample(logits, mask_bits, mask_idx, samp.temperature, samp.top_k,
                                 samp.top_p, samp.seed, samp.position, vocab_offset=self.vocab_offset)
             if samp.top_n >= 0:
+                if ed is not None:
+                    ops.logit_restore(logits, ed.row_start, ed.ent_id, ed.presence, ed.frequency, ed.repetition,
+                                      ed.pend_src, ed.tokens, saved, vocab_offset=self.vocab_offset)
                 samp.logprobs = ops.token_logprobs(logits, mask_bits, mask_idx, idx, samp.top_n,
                                                    vocab_offset=self.vocab_offset)
             return idx

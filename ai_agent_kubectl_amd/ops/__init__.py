@@ -379,6 +379,71 @@ def token_logprobs(logits: torch.Tensor, mask_bits: Optional[torch.Tensor], mask
     return (lp, top_id, top_lp, mx, cnt, mass) if return_probe else (lp, top_id, top_lp)
 
 
+def _check_edits(what: str, logits, row_start, per_entry, per_row, pend_src, tokens):
+    R = logits.shape[0]
+    dev = logits.device
+    if logits.dim() != 2 or not logits.is_contiguous() or logits.dtype != torch.bfloat16:
+        raise ValueError(f"{what}: logits must be contiguous bf16 [rows, vocab]")
+    E = per_entry[0][0].numel()
+    for t, dt in [(row_start, torch.int32)] + per_entry + per_row + [(pend_src, torch.int32), (tokens, torch.int32)]:
+        if t is None:
+            continue
+        if t.dtype != dt or t.device != dev or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f"{what}: every array must be a contiguous 1-d tensor of its dtype on {dev}")
+    if row_start.numel() != R + 1 or any(t.numel() != E for t, _ in per_entry) or any(t.numel() != R for t, _ in per_row):
+        raise ValueError(f"{what}: row_start is [rows + 1], the entry arrays [entries], the parameters [rows]")
+    if (pend_src is None) != (tokens is None) or (pend_src is not None and pend_src.numel() != R):
+        raise ValueError(f"{what}: pend_src [rows] and tokens come together")
+    return R, E
+
+
+def logit_adjust(logits: torch.Tensor, row_start: torch.Tensor, ent_id: torch.Tensor, ent_cnt: torch.Tensor,
+                 ent_bias: torch.Tensor, presence: torch.Tensor, frequency: torch.Tensor, repetition: torch.Tensor,
+                 pend_src: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None,
+                 vocab_offset: int = 0, save: bool = False) -> Optional[torch.Tensor]:
+    """presence / frequency / repetition penalties and logit_bias applied in place to the bf16 `logits`
+    [R, V] before the sampler reads them (csrc/logit_adjust.hip; semantics: ops/reference.py
+    `logit_adjust`).  CSR image: row_start int32 [R + 1]; per entry ent_id int32 (global id, distinct
+    within a row), ent_cnt int32 (bits 0-30 = occurrences in the output, bit 31 = occurs in the prompt),
+    ent_bias fp32; per row presence / frequency / repetition fp32.  pend_src int32 [R] with tokens int32:
+    pend_src[r] >= 0 names the row's newest output token tokens[pend_src[r]], which the entries do not
+    count.  save: -> bf16 [R + entries], the original patterns for logit_restore; else None."""
+    if _ref(logits):
+        return ref.logit_adjust(logits, row_start, ent_id, ent_cnt, ent_bias, presence, frequency, repetition, pend_src,
+                                tokens, vocab_offset, save=save)
+    lib = require()
+    R, E = _check_edits("logit_adjust", logits, row_start,
+                        [(ent_id, torch.int32), (ent_cnt, torch.int32), (ent_bias, torch.float32)],
+                        [(presence, torch.float32), (frequency, torch.float32), (repetition, torch.float32)],
+                        pend_src, tokens)
+    saved = torch.zeros(R + E, dtype=torch.bfloat16, device=logits.device) if save else None
+    check(lib.ka_logit_adjust(_p(logits), _p(row_start), _p(ent_id), _p(ent_cnt), _p(ent_bias), _p(presence),
+                              _p(frequency), _p(repetition), _p(pend_src), _p(tokens),
+                              tokens.numel() if tokens is not None else 0, _p(saved), R, E, logits.shape[1],
+                              int(vocab_offset), _stream()), "logit_adjust")
+    return saved
+
+
+def logit_restore(logits: torch.Tensor, row_start: torch.Tensor, ent_id: torch.Tensor, presence: torch.Tensor,
+                  frequency: torch.Tensor, repetition: torch.Tensor, pend_src: Optional[torch.Tensor],
+                  tokens: Optional[torch.Tensor], saved: torch.Tensor, vocab_offset: int = 0) -> None:
+    """Undo logit_adjust(save=True): the saved bf16 patterns go back, from the same image and the same
+    `tokens` (a step that also reports log-probabilities: between ops.sample and ops.token_logprobs)."""
+    if _ref(logits):
+        return ref.logit_restore(logits, row_start, ent_id, presence, frequency, repetition, pend_src, tokens, saved,
+                                 vocab_offset)
+    lib = require()
+    R, E = _check_edits("logit_restore", logits, row_start, [(ent_id, torch.int32)],
+                        [(presence, torch.float32), (frequency, torch.float32), (repetition, torch.float32)],
+                        pend_src, tokens)
+    if saved is None or saved.dtype != torch.bfloat16 or saved.device != logits.device or saved.numel() != R + E \
+            or not saved.is_contiguous():
+        raise ValueError("logit_restore: saved must be the bf16 [rows + entries] tensor logit_adjust returned")
+    check(lib.ka_logit_restore(_p(logits), _p(row_start), _p(ent_id), _p(presence), _p(frequency), _p(repetition),
+                               _p(pend_src), _p(tokens), tokens.numel() if tokens is not None else 0, _p(saved), R, E,
+                               logits.shape[1], int(vocab_offset), _stream()), "logit_restore")
+
+
 def argmax_combine(vals: torch.Tensor, idxs: torch.Tensor) -> torch.Tensor:
     """TP vocab-parallel greedy combine: vals / idxs [ranks, S] (every rank's best value and global token
     id) -> [S] int32 id of the largest value, the lowest id on ties (csrc/sampling.hip)."""

@@ -57,6 +57,10 @@ _SIGS = {
     "ka_sample_ws_words": [I, I],
     "ka_token_logprobs": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, I, P],
     "ka_token_logprobs_ws_words": [I, I, I],
+    "ka_logit_adjust": [P, P, P, P, P, P, P, P, P, P, I, P, I, I, I, I, P],
+    "ka_logit_restore": [P, P, P, P, P, P, P, P, I, P, I, I, I, I, P],
+    "ka_logit_adjust_batch": [],
+    "ka_logit_adjust_threads": [],
     "ka_moe_topk": [P, P, P, I, I, I, P],
     "ka_paged_decode": [P, P, P, P, P, I, P, I, I, I, I, I, F, P],
     "ka_paged_decode_rope": [P, P, P, I, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, P],

@@ -314,3 +314,105 @@ def token_logprobs(logits, mask_bits, mask_idx, token, top_n: int, vocab_offset:
     if return_probe:
         out += (mx, cnt, mass)
     return out
+
+
+# ---- penalties and logit_bias (csrc/logit_adjust.hip) ----
+PROMPT_BIT = 0x80000000   # bit 31 of an entry's cnt word: the token occurs in the prompt
+
+
+def _pending(pend_src, tokens, r: int) -> int:
+    """Global id of row r's pending token (tokens[pend_src[r]]), -1 without one."""
+    if pend_src is None or tokens is None:
+        return -1
+    ps = int(pend_src[r])
+    return int(tokens[ps]) if 0 <= ps < tokens.numel() else -1
+
+
+def _row_skipped(n_entries: int, pend: bool, pres: float, freq: float, rep: float) -> bool:
+    return n_entries == 0 and (not pend or (pres == 0.0 and freq == 0.0 and rep == 1.0))
+
+
+def logit_adjust(logits, row_start, ent_id, ent_cnt, ent_bias, presence, frequency, repetition, pend_src=None,
+                 tokens=None, vocab_offset: int = 0, save: bool = False):
+    """presence / frequency / repetition penalties and logit_bias, in place on bf16 `logits` [R, V]: THE
+    definition (csrc/logit_adjust.hip and the engine match it bit for bit).
+
+    Row r owns the entries row_start[r] .. row_start[r + 1]: `ent_id` (global token id, distinct within a
+    row), `ent_cnt` (int32: bits 0-30 = c, the token's occurrences in the sequence's output so far, the
+    jump-forward prefix included; bit 31 = it occurs in the prompt) and `ent_bias` (fp32, 0 without a
+    logit_bias entry); `presence`, `frequency`, `repetition` are fp32 [R].  With seen = c > 0 or the
+    prompt bit, every operation in fp32 and rounded separately, in this order:
+        x = float(logit)
+        if seen and repetition != 1:  x = x / repetition if x > 0 else x * repetition
+        x = x - frequency * float(c);  x = x - (presence if c > 0 else 0);  x = x + bias
+        logit = bf16 round-to-nearest-even(x)
+    Tokens without an entry do not change; an entry outside [vocab_offset, vocab_offset + V) is skipped.
+    An adjustment below half a bf16 ulp of the logit therefore leaves it as it is, and a touched -0
+    comes out as +0 (x + 0), which every consumer treats alike.
+    pend_src int32 [R] with tokens int32: pend_src[r] >= 0 says the row's newest output token is
+    tokens[pend_src[r]] and the entries do not count it: it gets c + 1 and seen, as one more entry
+    (c = 1, no prompt bit, bias 0) when no entry has its id.  A row without entries is left alone when
+    it has no pending token or its three parameters are neutral.
+    save: -> bf16 [R + entries], the original patterns (slot r: the pending token of row r when it had
+    no entry; slot R + e: entry e; slots never written hold 0) for logit_restore; else -> None."""
+    R, V = logits.shape
+    E = int(ent_id.numel())
+    saved = torch.zeros(R + E, dtype=logits.dtype, device=logits.device) if save else None
+    rs = row_start.tolist()
+    for r in range(R):
+        e0, e1 = max(0, rs[r]), min(E, rs[r + 1])
+        pres, freq, rep = presence[r].float(), frequency[r].float(), repetition[r].float()
+        pend = _pending(pend_src, tokens, r)
+        if _row_skipped(max(0, e1 - e0), pend >= 0, float(pres), float(freq), float(rep)):
+            continue
+        ids = ent_id[e0:e1].long()
+        word = ent_cnt[e0:e1].long() & 0xFFFFFFFF
+        c = word & (PROMPT_BIT - 1)
+        prompt = (word & PROMPT_BIT) != 0
+        bias = ent_bias[e0:e1].float()
+        slot = torch.arange(e0, e1, device=logits.device) + R
+        if pend >= 0:
+            hit = ids == pend
+            if bool(hit.any()):
+                c = c + hit.long()
+            else:
+                ids = torch.cat([ids, ids.new_tensor([pend])])
+                c = torch.cat([c, c.new_tensor([1])])
+                prompt = torch.cat([prompt, prompt.new_tensor([False])])
+                bias = torch.cat([bias, bias.new_zeros(1)])
+                slot = torch.cat([slot, slot.new_tensor([r])])
+        li = ids - vocab_offset
+        ok = (li >= 0) & (li < V)
+        li, c, prompt, bias, slot = li[ok], c[ok], prompt[ok], bias[ok], slot[ok]
+        raw = logits[r, li]
+        if save:
+            saved[slot] = raw
+        x = raw.float()
+        if float(rep) != 1.0:
+            x = torch.where(prompt | (c > 0), torch.where(x > 0, x / rep, x * rep), x)
+        x = x - freq * c.float()
+        x = x - torch.where(c > 0, pres, torch.zeros_like(pres))
+        x = x + bias
+        logits[r, li] = x.to(logits.dtype)
+    return saved
+
+
+def logit_restore(logits, row_start, ent_id, presence, frequency, repetition, pend_src, tokens, saved,
+                  vocab_offset: int = 0) -> None:
+    """Write back what logit_adjust(save=True) saved, from the same image and the same `tokens`."""
+    R, V = logits.shape
+    E = int(ent_id.numel())
+    rs = row_start.tolist()
+    for r in range(R):
+        e0, e1 = max(0, rs[r]), min(E, rs[r + 1])
+        pend = _pending(pend_src, tokens, r)
+        if _row_skipped(max(0, e1 - e0), pend >= 0, float(presence[r]), float(frequency[r]), float(repetition[r])):
+            continue
+        ids = ent_id[e0:e1].long()
+        slot = torch.arange(e0, e1, device=logits.device) + R
+        if pend >= 0 and not bool((ids == pend).any()):
+            ids = torch.cat([ids, ids.new_tensor([pend])])
+            slot = torch.cat([slot, slot.new_tensor([r])])
+        li = ids - vocab_offset
+        ok = (li >= 0) & (li < V)
+        logits[r, li[ok]] = saved[slot[ok]]
