@@ -18,6 +18,11 @@ gets 422; logprobs on a tensor-parallel engine get 400.
 `logit_bias` ({"<token id>": -100..100}, at most 300 entries) edit the logits before the token is chosen, also
 at temperature 0 (csrc/logit_adjust.hip); `logprobs` stay the model's raw ones.  Out-of-range values and
 non-integer keys get 422; a token id past the vocabulary and any of the four on a tensor-parallel engine get 400.
+`guided_regex` (a pattern of at most 2048 characters) or `guided_choice` (1..256 strings of 1..256 bytes), vLLM's
+fields, constrain the completion (engine/guided.py, csrc/guide_mask.hip): with finish_reason "stop" the content
+matches the pattern / is one of the choices, with "length" it is a prefix of a match.  Both together, an empty
+string or list and a cap violation get 422; a pattern outside the dialect, one the tokenizer cannot spell, a full
+guide table and a tensor-parallel engine get 400.
 Auth: when API_AUTH_KEY is set, `Authorization: Bearer <key>` or `X-API-Key: <key>`.
 """
 from __future__ import annotations
@@ -50,6 +55,16 @@ class ChatRequest(BaseModel):
     frequency_penalty: Optional[float] = Field(0.0, ge=-2.0, le=2.0)
     repetition_penalty: Optional[float] = Field(1.0, gt=0.0, le=2.0)
     logit_bias: Optional[Dict[str, float]] = None   # OpenAI's wire form: decimal token-id strings -> bias
+    guided_regex: Optional[str] = Field(None, min_length=1, max_length=2048)
+    guided_choice: Optional[List[str]] = Field(None, min_length=1, max_length=256)
+
+    @field_validator("guided_choice")
+    @classmethod
+    def _guided_choice_entries(cls, v):
+        for c in v or ():
+            if not 1 <= len(c.encode("utf-8")) <= 256:
+                raise ValueError("every guided_choice entry must be 1..256 bytes long")
+        return v
 
     @field_validator("logit_bias")
     @classmethod
@@ -69,6 +84,8 @@ class ChatRequest(BaseModel):
     def _top_logprobs_needs_logprobs(self):
         if self.top_logprobs is not None and not self.logprobs:
             raise ValueError("top_logprobs requires logprobs: true")
+        if self.guided_regex is not None and self.guided_choice is not None:
+            raise ValueError("guided_regex and guided_choice cannot be combined")
         return self
 
 
@@ -108,6 +125,10 @@ def install(app, svc, settings) -> None:
                    logit_bias=bias or None)
         if pen != _NEUTRAL:   # only when sent: a plain request is submitted exactly as it always was
             kw.update(pen)
+        if req.guided_regex is not None:
+            kw["guided_regex"] = req.guided_regex
+        if req.guided_choice is not None:
+            kw["guided_choice"] = list(req.guided_choice)
         content = None
         try:
             if req.logprobs:
@@ -117,7 +138,7 @@ def install(app, svc, settings) -> None:
                     msgs, top_logprobs=req.top_logprobs or 0, **kw)
             else:
                 text, finish, n_in, n_out = await backend.generate_chat(msgs, **kw)
-        except ValueError as e:   # a request this engine cannot serve (sampling / logprobs / penalties under TP > 1)
+        except ValueError as e:   # a request this engine cannot serve (sampling / logprobs / penalties / guides under TP > 1, a bad pattern)
             raise HTTPException(status_code=400, detail=str(e))
         choice = {"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": finish}
         if content is not None:   # only when asked for: the response is otherwise what it always was

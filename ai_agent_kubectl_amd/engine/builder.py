@@ -44,6 +44,7 @@ class EngineOptions:
     safe_decode: bool = True
     ignore_eos: bool = False
     prefix_caching: bool = True
+    guide_states: int = 8192       # DFA states of the guided-decoding arena (512 bytes each; engine/guided.py)
 
     @classmethod
     def from_settings(cls, s) -> "EngineOptions":
@@ -54,6 +55,7 @@ class EngineOptions:
                    safe_decode=s.SAFE_DECODE, ignore_eos=s.IGNORE_EOS, prefix_caching=s.PREFIX_CACHING,
                    kv_cache_tokens=int(os.environ.get("KV_CACHE_TOKENS", 0)),
                    max_model_len=int(os.environ.get("MAX_MODEL_LEN", 8192)),
+                   guide_states=int(os.environ.get("GUIDE_STATES", 8192)),
                    device="cuda" if torch.cuda.is_available() else "cpu")
 
 
@@ -106,7 +108,8 @@ def build_engine(opts: EngineOptions, comm=None, metrics=None) -> LLMEngine:
     runner = ModelRunner(cfg, weights, dev, num_blocks=num_blocks, block_size=opts.block_size,
                          max_model_len=opts.max_model_len, graph_buckets=opts.graph_buckets, mask_bits=masks,
                          comm=comm, tp_rank=opts.tp_rank, tp_size=opts.tp_size, ep_rank=par.ep_rank,
-                         ep_size=ep_size, use_graphs=opts.use_graphs)
+                         ep_size=ep_size, use_graphs=opts.use_graphs, tokenizer=tok,
+                         guide_states=opts.guide_states)
     step_tokens = opts.max_batched_tokens if opts.max_batched_tokens > 0 else cfg.default_step_tokens()
     eng = LLMEngine(runner, tok, max_batch=opts.max_batch, max_batched_tokens=step_tokens,
                     max_model_len=opts.max_model_len, prefix_caching=opts.prefix_caching, metrics=metrics)

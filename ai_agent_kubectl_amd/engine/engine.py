@@ -31,7 +31,7 @@ import threading
 import time
 from typing import Callable, Dict, List, Optional
 
-from . import penalties
+from . import guided, penalties
 from .block_manager import make_block_manager
 from .runner import CollectiveTimeout, ModelRunner
 from .scheduler import Scheduler
@@ -170,8 +170,13 @@ class LLMEngine:
                 # the logits are vocab-parallel: the ranks' (max, mass) pairs would have to be combined
                 raise ValueError("logprobs are not supported with tensor parallelism (TP > 1)")
         penalties.validate(params, self.runner.cfg.vocab_size, self.runner.tp_size)
+        guided.validate(params, self.tokenizer, self.runner.tp_size, forced_prefix)
+        # a guided request holds its guide's range of the device arena from here until it leaves (_finish,
+        # abort); a table with no range left to free refuses it (ValueError)
+        ref = self.runner.guides().acquire(params.guide) if params.guide is not None else None
         seq = Sequence(prompt_ids=list(prompt_ids), params=params, callback=callback,
                        forced_prefix=list(forced_prefix or []))
+        seq.guide_ref = ref
         self._inbox.put(("add", seq))
         self._wake.set()
         return seq
@@ -189,6 +194,7 @@ class LLMEngine:
                 return
             if op == "add":
                 if seq.finished:
+                    self._release_guide(seq)
                     continue
                 try:
                     self.scheduler.add(seq)
@@ -199,8 +205,15 @@ class LLMEngine:
                 self.scheduler.abort(seq)
                 seq.finish_reason = "abort"
                 self._live.pop(seq.seq_id, None)
+                self._release_guide(seq)
+
+    def _release_guide(self, seq: Sequence) -> None:
+        ref, seq.guide_ref = seq.guide_ref, None
+        if ref is not None:
+            self.runner.guide_table.release(ref)
 
     def _finish(self, seq: Sequence, status: SeqStatus, reason: str, error: Optional[BaseException] = None):
+        self._release_guide(seq)
         seq.status = status
         seq.finish_reason = reason
         seq.error = error

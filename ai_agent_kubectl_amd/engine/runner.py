@@ -16,6 +16,7 @@ from __future__ import annotations
 import bisect
 import logging
 import os
+import threading
 import time
 from typing import Dict, List, NamedTuple, Optional
 
@@ -24,11 +25,12 @@ import torch
 
 from ..models.config import ModelConfig
 from .. import ops
-from ..models.llama import SAMP_WORDS, AttnMeta, LlamaModel, LogitEdits, SampleArrays
+from ..models.llama import SAMP_WORDS, AttnMeta, GuideArrays, LlamaModel, LogitEdits, SampleArrays
 from ..ops.autotune import tune_engine
 
 logger = logging.getLogger("app.engine")
 from ..parallel.comm import LocalComm
+from .guided import GUIDE_STATES, GuideTable, pack_guides
 from .penalties import pack_edits
 from .safe_decode import mask_index_for
 from .scheduler import Batch
@@ -86,7 +88,8 @@ class ModelRunner:
     def __init__(self, cfg: ModelConfig, weights: Dict[str, torch.Tensor], device: torch.device,
                  num_blocks: int, block_size: int = 16, max_model_len: int = 4096, graph_buckets=(1, 2, 4, 8),
                  mask_bits: Optional[np.ndarray] = None, comm=None, tp_rank: int = 0, tp_size: int = 1,
-                 ep_rank: int = 0, ep_size: int = 1, use_graphs: bool = True):
+                 ep_rank: int = 0, ep_size: int = 1, use_graphs: bool = True, tokenizer=None,
+                 guide_states: int = GUIDE_STATES):
         self.cfg = cfg
         self.device = torch.device(device)
         self.comm = comm or LocalComm()
@@ -162,6 +165,16 @@ class ModelRunner:
         # pinned and double-buffered like the prefill metadata, grown on demand (_stage_edits)
         self._h_pen: List[Optional[torch.Tensor]] = [None, None]
         self._nflip = 0
+        # guided decoding: the vocabulary's token table and the DFA arena (engine/guided.py GuideTable, created
+        # with the first guided request: guides()), and the pinned, double-buffered per-row image of a step
+        # with a guided request (_stage_guides).  A step without one touches none of them
+        self.tokenizer = tokenizer
+        self.guide_states = int(guide_states)
+        self.guide_table: Optional[GuideTable] = None
+        self.token_table = None
+        self._guide_lock = threading.Lock()
+        self._h_gds: List[Optional[torch.Tensor]] = [None, None]
+        self._gflip = 0
         # the records of the step read back last (collect / execute), for engine._settle to take
         self.last_logprobs: Optional[StepLogprobs] = None
         self.d_hdr = torch.zeros(HDR, dtype=torch.int32, device=self.device)
@@ -181,7 +194,7 @@ class ModelRunner:
         self.graph_pool = None
         self.stats = {"decode_steps": 0, "prefill_steps": 0, "graph_replays": 0, "decode_ms": 0.0,
                       "prefill_ms": 0.0, "prefill_tokens": 0, "persistent_stalls": 0, "sampled_steps": 0,
-                      "logprob_steps": 0, "penalty_steps": 0}
+                      "logprob_steps": 0, "penalty_steps": 0, "guided_steps": 0}
         # bucket -> the captured graph holds the persistent decode kernel (its error word must be read
         # back on every replay of that graph, whatever model.persistent says now)
         self.graph_persistent: Dict[int, bool] = {}
@@ -246,19 +259,57 @@ class ModelRunner:
         (the masked argmax, bit for bit)."""
         top_n = self._logprob_n(batch)
         penalised = any(s.params.penalised for s in batch.seqs)
-        if top_n < 0 and not penalised and not self._sampling(batch):
+        guided = any(s.params.guide is not None for s in batch.seqs)
+        if top_n < 0 and not penalised and not guided and not self._sampling(batch):
             return None
         if self.tp_size > 1:
-            raise RuntimeError("sampling with temperature > 0, logprobs and penalties are not wired through "
-                               "the TP worker protocol")
+            raise RuntimeError("sampling with temperature > 0, logprobs, penalties and guides are not wired "
+                               "through the TP worker protocol")
         self.stats["sampled_steps"] += self._sampling(batch)
         self.stats["logprob_steps"] += top_n >= 0
         self.stats["penalty_steps"] += penalised
+        self.stats["guided_steps"] += guided
         samp = self._stage_samp_arrays(batch, rows, ahead)
         samp.top_n = top_n
         if penalised:
             samp.edits = self._stage_edits(batch, rows, pend)
+        if guided:
+            samp.guide = self._stage_guides(batch, rows, pend)
         return samp
+
+    def guides(self) -> GuideTable:
+        """The DFA arena and the token table, built with the first guided request (any thread)."""
+        with self._guide_lock:
+            if self.guide_table is None:
+                if self.tokenizer is None:
+                    raise ValueError("guided decoding needs the engine's tokenizer (ModelRunner(tokenizer=...))")
+                self.token_table = ops.token_table(self.tokenizer.id_to_bytes, self.tokenizer.eos_ids, self.device)
+                self.guide_table = GuideTable(self.guide_states, self.device)
+            return self.guide_table
+
+    def _stage_guides(self, batch: Batch, rows: int, pend: Optional[List[int]]) -> GuideArrays:
+        """The step's guide image (engine/guided.py pack_guides) -> device without a host sync, through one of
+        two pinned buffers like the penalty image.  Guides placed since the last step are uploaded here, on the
+        engine's stream: behind every queued step that could still read the range they reuse.  A sequence that
+        did not come through engine.submit takes its placement here."""
+        table = self.guides()
+        for s in batch.seqs:
+            if s.params.guide is not None and s.guide_ref is None and not s.finished:
+                s.guide_ref = table.acquire(s.params.guide)
+        table.flush()
+        img = pack_guides(batch.seqs, rows, pend, self.tokenizer)
+        if self.device.type != "cuda":
+            dimg = torch.from_numpy(img)
+        else:
+            n = img.shape[0]
+            k = self._gflip = self._gflip ^ 1
+            hb = self._h_gds[k]
+            if hb is None or hb.numel() < n:
+                hb = torch.empty(max(n, 4 * self.bmax), dtype=torch.int32, pin_memory=True)
+                self._h_gds[k] = hb
+            hb.numpy()[:n] = img
+            dimg = hb[:n].to(self.device, non_blocking=True)
+        return GuideArrays.from_image(dimg, rows, self.token_table, table.trans, table.accept, self.d_out)
 
     def _stage_edits(self, batch: Batch, rows: int, pend: Optional[List[int]]) -> LogitEdits:
         """The step's penalty / logit_bias image (engine/penalties.py pack_edits) -> device without a host

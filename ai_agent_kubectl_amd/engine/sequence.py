@@ -43,6 +43,9 @@ class SamplingParams:
     frequency_penalty: float = 0.0    # -2..2: times c, subtracted
     repetition_penalty: float = 1.0   # 0 < r <= 2 (vLLM / HF): a token of the prompt or the output: l / r if l > 0 else l * r
     logit_bias: Optional[Dict[int, float]] = None   # token id -> -100..100, at most 300 entries; added last
+    # guided decoding (csrc/guide_mask.hip): a compiled engine/guided.py Guide (compile_regex / compile_choice);
+    # every step's token mask then also admits only tokens that keep the output a prefix of a match
+    guide: Optional[object] = None
 
     @property
     def penalised(self) -> bool:
@@ -85,6 +88,10 @@ class Sequence:
     logprobs: List[TokenLogprob] = field(default_factory=list)
     # params.penalised: the per-sequence part of the penalty image (engine/penalties.py PenaltyState)
     penalty_state: Optional[object] = None
+    # params.guide: the DFA state after the final output tokens (engine/guided.py GuideState) and the
+    # guide's placement in the device arena (GuideTable.acquire; released when the sequence leaves)
+    guide_state: Optional[object] = None
+    guide_ref: Optional[object] = None
 
     def __post_init__(self):
         seed = self.params.seed if self.params.seed is not None else random.getrandbits(64)

@@ -11,9 +11,13 @@ Cancellation (the service's `LLM_TIMEOUT` -> 504) aborts the sequence and frees 
 from __future__ import annotations
 
 import asyncio
+import collections
+import concurrent.futures
 import logging
+import threading
 from typing import List, Optional
 
+from ..engine import guided
 from ..engine.safe_decode import forced_prefix
 from ..engine.sequence import SamplingParams
 from ..prompt import PROMPT_PREFIX, PROMPT_SUFFIX
@@ -34,6 +38,10 @@ class EngineLLM(LLMBackend):
         self._after_ids: List[int] = after
         self._forced = forced_prefix(self.tok) if safe_decode else []
         self._started = False
+        # compiled guides of guided_regex / guided_choice requests, by source (LRU, GUIDE_CACHE entries)
+        self._guides: "collections.OrderedDict" = collections.OrderedDict()
+        self._guides_lock = threading.Lock()
+        self._compiling: dict = {}   # source -> Future of a compilation in progress
 
     @classmethod
     def from_settings(cls, settings, metrics=None) -> "EngineLLM":
@@ -123,9 +131,12 @@ class EngineLLM(LLMBackend):
         """Returns (text, finish_reason, prompt_tokens, completion_tokens).  temperature 0 (the default)
         decodes greedily; above it the engine samples (top_k / top_p cuts, `seed` makes it repeatable).
         penalties: presence_penalty, frequency_penalty, repetition_penalty, logit_bias ({token id: bias}),
-        applied to the logits before the token is chosen, also at temperature 0 (SamplingParams).
-        Raises ValueError for a request the engine cannot serve (temperature > 0 or penalties under
-        TP > 1, a logit_bias id outside the vocabulary)."""
+        applied to the logits before the token is chosen, also at temperature 0 (SamplingParams); and
+        guided_regex or guided_choice: the completion then matches the pattern / is one of the choices when it
+        ends with "stop", and is a prefix of a match when max_tokens cuts it (engine/guided.py).
+        Raises ValueError for a request the engine cannot serve (temperature > 0, penalties or a guide under
+        TP > 1, a logit_bias id outside the vocabulary, a pattern outside the dialect or that the tokenizer
+        cannot spell, a full guide table)."""
         seq, n_in = await self._chat(messages, max_tokens, safe, temperature, top_p, top_k, seed, None, **penalties)
         out = [t for t in seq.output_ids if not self.tok.is_eos(t)]
         return self.tok.decode(out), ("stop" if seq.finish_reason == "stop" else "length"), n_in, len(seq.output_ids)
@@ -158,20 +169,66 @@ class EngineLLM(LLMBackend):
         return (tok.decode(out), ("stop" if seq.finish_reason == "stop" else "length"), n_in, len(seq.output_ids),
                 content)
 
+    GUIDE_CACHE = 64
+
+    def compile_guide(self, guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None):
+        """The compiled guide of a request (engine/guided.py), from an LRU of the last GUIDE_CACHE sources; the
+        first guided request also builds the engine's token table and guide arena here.  Host work that the
+        compiler's caps and work budget keep to a fraction of a second (the token table: once per engine):
+        `_chat` runs it on a worker thread, off the event loop and off the engine's loop.  Requests that arrive
+        with a source that is being compiled wait for that compilation.  Raises ValueError for a pattern
+        outside the dialect or past a cap."""
+        if guided_regex is not None and guided_choice is not None:
+            raise ValueError("guided_regex and guided_choice cannot be combined")
+        key = ("regex", guided_regex) if guided_regex is not None else ("choice", tuple(guided_choice))
+        with self._guides_lock:
+            g = self._guides.get(key)
+            if g is not None:
+                self._guides.move_to_end(key)
+                return g
+            fut = self._compiling.get(key)
+            mine = fut is None
+            if mine:
+                fut = self._compiling[key] = concurrent.futures.Future()
+        if not mine:
+            return fut.result()
+        try:
+            g = (guided.compile_regex(guided_regex) if guided_regex is not None
+                 else guided.compile_choice(list(guided_choice)))
+            if self.engine.runner.tp_size == 1:   # a TP engine refuses the request at submit: nothing to build
+                self.engine.runner.guides()
+        except BaseException as e:
+            with self._guides_lock:
+                del self._compiling[key]
+            fut.set_exception(e)
+            raise
+        with self._guides_lock:
+            self._guides[key] = g
+            self._guides.move_to_end(key)
+            while len(self._guides) > self.GUIDE_CACHE:
+                self._guides.popitem(last=False)
+            del self._compiling[key]
+        fut.set_result(g)
+        return g
+
     async def _chat(self, messages, max_tokens, safe, temperature, top_p, top_k, seed, logprobs,
                     presence_penalty: float = 0.0, frequency_penalty: float = 0.0, repetition_penalty: float = 1.0,
-                    logit_bias=None):
+                    logit_bias=None, guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None):
         """Submit one chat request and wait for it -> (finished sequence, prompt tokens)."""
         if not self._started:
             await self.start()
         loop = asyncio.get_running_loop()
+        guide = None
+        if guided_regex is not None or guided_choice is not None:
+            guide = await loop.run_in_executor(None, self.compile_guide, guided_regex, guided_choice)
         fut: asyncio.Future = loop.create_future()
         params = SamplingParams(max_new_tokens=max_tokens, ignore_eos=False, safe_decode=safe,
                                 temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=seed,
                                 logprobs=logprobs, presence_penalty=float(presence_penalty),
                                 frequency_penalty=float(frequency_penalty),
                                 repetition_penalty=float(repetition_penalty),
-                                logit_bias={int(t): float(b) for t, b in logit_bias.items()} if logit_bias else None)
+                                logit_bias={int(t): float(b) for t, b in logit_bias.items()} if logit_bias else None,
+                                guide=guide)
         ids = self.chat_ids(messages)
         seq = self.engine.submit(ids, params, lambda sq: loop.call_soon_threadsafe(_resolve, fut, sq),
                                  forced_prefix=self._forced if safe else None)

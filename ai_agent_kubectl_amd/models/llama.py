@@ -88,6 +88,29 @@ class LogitEdits:
 
 
 @dataclass
+class GuideArrays:
+    """The guided rows of a step (ops.guide_mask), on the logits' device: the vocabulary's token table, the
+    DFA arena and per row the guide's arena base (-1: the row is not guided), its states, the row's state
+    and the slot of its newest token when that is still on the device."""
+    table: object                      # ops.TokenTable
+    arena_trans: torch.Tensor          # int16 [GUIDE_STATES, 256]
+    arena_accept: torch.Tensor         # uint8 [GUIDE_STATES]
+    row_base: torch.Tensor             # int32 [S]
+    row_nstates: torch.Tensor          # int32 [S]
+    row_state: torch.Tensor            # int32 [S]
+    pend_src: torch.Tensor             # int32 [S]: >= 0: the row's newest output token is tokens[pend_src], not walked yet
+    tokens: torch.Tensor               # int32: the runner's d_out
+    state_after: Optional[torch.Tensor] = None   # set by LlamaModel.sample: the state each row's mask was built from
+
+    @classmethod
+    def from_image(cls, img: torch.Tensor, rows: int, table, arena_trans, arena_accept, tokens) -> "GuideArrays":
+        """Views of a packed int32 image [base | nstates | state | pend_src] (rows each)."""
+        v = [img[i * rows:(i + 1) * rows] for i in range(4)]
+        return cls(table=table, arena_trans=arena_trans, arena_accept=arena_accept, row_base=v[0], row_nstates=v[1],
+                   row_state=v[2], pend_src=v[3], tokens=tokens)
+
+
+@dataclass
 class SampleArrays:
     """Per-row sampling arrays of a step (ops.sample), [S] each on the logits' device."""
     temperature: torch.Tensor          # fp32, 0 = greedy
@@ -98,6 +121,7 @@ class SampleArrays:
     top_n: int = -1                    # >= 0: also report log-probabilities, with this many alternatives per row
     logprobs: Optional[tuple] = None   # set by LlamaModel.sample when top_n >= 0: (lp [S], top_id, top_lp [S, top_n])
     edits: Optional[LogitEdits] = None   # a step with a penalty / logit_bias request: applied before the sampler
+    guide: Optional[GuideArrays] = None  # a step with a guided request: its rows' masks are built first
 
     @classmethod
     def from_image(cls, img: torch.Tensor, cap: int, n: int) -> "SampleArrays":
@@ -373,10 +397,18 @@ class LlamaModel:
         of the step, and leaves its outputs in samp.logprobs.  A step with a penalty / logit_bias request
         (samp.edits) also takes this route: ops.logit_adjust edits the written logits before the sampler
         reads them (the mask still wins: a forbidden token stays forbidden whatever its bias), and
-        ops.logit_restore puts the model's own logits back before the log-probabilities are taken."""
+        ops.logit_restore puts the model's own logits back before the log-probabilities are taken.  A step
+        with a guided request (samp.guide) builds its rows' masks first: ops.guide_mask's (bits, idx) stand in
+        for (mask_bits, mask_idx) in everything below, so the guide is part of the token mask: the SAFE_DECODE
+        rows still apply inside it, and log-probabilities are the model's distribution under it."""
         if samp is not None:
             if self.tp_size != 1:
                 raise RuntimeError("sampling with temperature > 0 is not wired through the TP worker protocol")
+            gd = samp.guide
+            if gd is not None:
+                mask_bits, mask_idx, gd.state_after = ops.guide_mask(
+                    gd.table, gd.arena_trans, gd.arena_accept, gd.row_base, gd.row_nstates, gd.row_state, gd.pend_src,
+                    gd.tokens, mask_bits, mask_idx if mask_bits is not None else None)
             logits = self.logits(hidden_last)
             ed, saved = samp.edits, None
             if ed is not None:

@@ -444,6 +444,110 @@ def logit_restore(logits: torch.Tensor, row_start: torch.Tensor, ent_id: torch.T
                                logits.shape[1], int(vocab_offset), _stream()), "logit_restore")
 
 
+class TokenTable:
+    """The vocabulary's byte strings for ops.guide_mask, built once per engine (`token_table`).
+    Host side (the reference and the CPU path): mat uint8 [V, longest] (zero padded), lens int32 [V] (0: the
+    token spells nothing), eos bool [V].  Device side (csrc/guide_mask.hip): rec int32 [V, 4], one 16-byte
+    record per token (byte 0: bits 0-4 = length 0..15 or 31 = longer, bit 7 = EOS id; bytes 1-15 = the
+    bytes; a longer token: bytes 4-7 = offset into `ovf`, bytes 8-11 = length) and ovf uint8, the pool of
+    the tokens longer than 15 bytes."""
+
+    INLINE = 15
+    LONG = 31
+    EOS = 0x80
+
+    def __init__(self, id_to_bytes, eos_ids, device="cpu"):
+        import numpy as np
+        V = self.vocab = len(id_to_bytes)
+        self.eos_ids = tuple(int(e) for e in eos_ids)
+        if not self.eos_ids or not all(0 <= e < V for e in self.eos_ids):
+            raise ValueError("token_table: eos_ids must name at least one id inside the vocabulary")
+        # packed with numpy over the concatenated bytes: no Python work per token beyond len() and the join
+        lens = np.asarray([len(p) if p else 0 for p in id_to_bytes], dtype=np.int32)
+        self.lens = lens
+        flat = np.frombuffer(b"".join(p for p in id_to_bytes if p), dtype=np.uint8)
+        starts = np.cumsum(lens, dtype=np.int64) - lens
+        owner = np.repeat(np.arange(V, dtype=np.int64), lens)
+        col = np.arange(flat.shape[0], dtype=np.int64) - np.repeat(starts, lens)
+        self.mat = np.zeros((V, max(1, int(lens.max()) if V else 1)), dtype=np.uint8)
+        self.mat[owner, col] = flat
+        rec = np.zeros((V, 16), dtype=np.uint8)
+        short = lens <= self.INLINE
+        rec[:, 0] = np.where(short, lens, self.LONG)
+        w = min(self.INLINE, self.mat.shape[1])
+        rec[:, 1:1 + w] = np.where(short[:, None], self.mat[:, :w], 0)
+        long_len = np.where(short, 0, lens).astype(np.int64)
+        offs = np.cumsum(long_len) - long_len
+        where = np.flatnonzero(~short)
+        rec[where, 4:12] = np.stack([offs[where], long_len[where]], axis=1).astype("<u4").view(np.uint8).reshape(-1, 8)
+        pool = flat[~short[owner]].tobytes()
+        self.eos = np.zeros(V, dtype=bool)
+        self.eos[list(self.eos_ids)] = True
+        rec[self.eos, 0] |= self.EOS
+        self.ovf_bytes = len(pool)
+        self.rec = torch.from_numpy(rec.view(np.int32)).to(device)
+        self.ovf = torch.from_numpy(np.frombuffer(bytes(pool) or b"\0", dtype=np.uint8).copy()).to(device)
+
+
+def token_table(id_to_bytes, eos_ids, device="cpu") -> TokenTable:
+    """id_to_bytes: per token id its bytes or None; eos_ids: the ids that end a completion (the first one is
+    what an empty mask row falls back to)."""
+    return TokenTable(id_to_bytes, eos_ids, device)
+
+
+def guide_mask(table: TokenTable, arena_trans: torch.Tensor, arena_accept: torch.Tensor, row_base: torch.Tensor,
+               row_nstates: torch.Tensor, row_state: torch.Tensor, pend_src: Optional[torch.Tensor] = None,
+               tokens: Optional[torch.Tensor] = None, base_bits: Optional[torch.Tensor] = None,
+               base_idx: Optional[torch.Tensor] = None):
+    """Per-row token masks of a step with guided rows (csrc/guide_mask.hip; semantics: ops/reference.py
+    `guide_mask`).  arena_trans int16 [G, 256] (the uint16 patterns), arena_accept uint8 [G]; row_base /
+    row_nstates / row_state int32 [R] (row_base < 0: the row is not guided); pend_src int32 [R] with tokens
+    int32: a pend_src[r] inside [0, len(tokens)) names the row's newest output token, walked first;
+    base_bits int32 [n_static, words] with base_idx int32 [R]: the SAFE_DECODE table and the rows' indices.
+    -> (bits int32 [n_static + R, words], idx int32 [R], state_after int32 [R]): what the samplers take as
+    (mask_bits, mask_idx), and the state each guided row's mask was built from (-1 = dead)."""
+    if _ref(row_base):
+        return ref.guide_mask(table, arena_trans, arena_accept, row_base, row_nstates, row_state, pend_src, tokens,
+                              base_bits, base_idx)
+    lib = require()
+    dev = row_base.device
+    R = row_base.numel()
+    words = (table.vocab + 31) // 32
+    per_row = [row_base, row_nstates, row_state] + ([pend_src] if pend_src is not None else []) \
+        + ([base_idx] if base_idx is not None else [])
+    for t in per_row + ([tokens] if tokens is not None else []):
+        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f"guide_mask: every per-row array must be a contiguous 1-d int32 tensor on {dev}")
+    if any(t.numel() != R for t in per_row):
+        raise ValueError("guide_mask: row_base, row_nstates, row_state, pend_src and base_idx are [rows]")
+    if (pend_src is None) != (tokens is None):
+        raise ValueError("guide_mask: pend_src [rows] and tokens come together")
+    if arena_trans.dtype != torch.int16 or arena_trans.dim() != 2 or arena_trans.shape[1] != 256 \
+            or not arena_trans.is_contiguous() or arena_trans.device != dev or arena_accept.dtype != torch.uint8 \
+            or arena_accept.shape != (arena_trans.shape[0],) or arena_accept.device != dev \
+            or not arena_accept.is_contiguous():
+        raise ValueError(f"guide_mask: the arena is int16 [states, 256] with uint8 [states] accept flags on {dev}")
+    if table.rec.device != dev:
+        raise ValueError(f"guide_mask: the token table lives on {table.rec.device}, the rows on {dev}")
+    n_static = 0
+    if base_bits is not None:
+        if base_bits.dtype != torch.int32 or base_bits.dim() != 2 or base_bits.shape[1] != words \
+                or base_bits.device != dev or not base_bits.is_contiguous() or base_idx is None:
+            raise ValueError(f"guide_mask: base_bits must be contiguous int32 [rows of masks, {words}] with base_idx")
+        n_static = base_bits.shape[0]
+    bits = torch.empty((n_static + R, words), dtype=torch.int32, device=dev)
+    if n_static:
+        bits[:n_static].copy_(base_bits)
+    idx = torch.empty(R, dtype=torch.int32, device=dev)
+    after = torch.empty(R, dtype=torch.int32, device=dev)
+    check(lib.ka_guide_mask(_p(bits), _p(idx), _p(after), _p(table.rec), _p(table.ovf) if table.ovf_bytes else None,
+                            table.ovf_bytes, table.vocab, table.eos_ids[0], _p(arena_trans), _p(arena_accept),
+                            arena_trans.shape[0], _p(row_base), _p(row_nstates), _p(row_state), _p(pend_src),
+                            _p(tokens), tokens.numel() if tokens is not None else 0, _p(base_bits),
+                            _p(base_idx) if base_bits is not None else None, n_static, R, _stream()), "guide_mask")
+    return bits, idx, after
+
+
 def argmax_combine(vals: torch.Tensor, idxs: torch.Tensor) -> torch.Tensor:
     """TP vocab-parallel greedy combine: vals / idxs [ranks, S] (every rank's best value and global token
     id) -> [S] int32 id of the largest value, the lowest id on ties (csrc/sampling.hip)."""

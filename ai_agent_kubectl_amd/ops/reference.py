@@ -416,3 +416,97 @@ def logit_restore(logits, row_start, ent_id, presence, frequency, repetition, pe
         li = ids - vocab_offset
         ok = (li >= 0) & (li < V)
         logits[r, li[ok]] = saved[slot[ok]]
+
+
+def guide_mask(table, arena_trans, arena_accept, row_base, row_nstates, row_state, pend_src, tokens, base_bits,
+               base_idx):
+    """The definition of ops.guide_mask (csrc/guide_mask.hip): per guided row the vocabulary bitmask of the
+    tokens that keep the row's DFA alive, intersected with the row's SAFE_DECODE mask.
+
+    table: ops.TokenTable (byte strings of the V tokens, EOS ids).  arena_trans int16 [G, 256] (uint16
+    patterns, 0xFFFF = dead, local state numbers), arena_accept uint8 [G]; per row: row_base (arena base, < 0
+    = not guided), row_nstates, row_state (local, outside [0, nstates) = dead), pend_src (None or int32: a
+    value in [0, n_tokens) names tokens[pend_src], the row's newest token, walked first: an EOS id leaves the
+    state, an id outside [0, V) or a token without bytes kills it).  base_bits int32 [n_static, words] or
+    None with base_idx int32 [R] (< 0 = no base row).
+    -> bits int32 [n_static + R, words] (rows 0..n_static-1 = base_bits, row n_static + r = batch row r, zero
+    for a row that is not guided; bit t set when (t is an EOS id and the state is live and accepting, or t
+    has bytes and they never reach dead) and the base row allows t; an empty row gets eos_ids[0]),
+    idx int32 [R] (n_static + r for a guided row, else base_idx[r] or -1), state_after int32 [R] (-1 = dead
+    or not guided).  Vectorised by byte position over the tokens still alive."""
+    import numpy as np
+    V, words = table.vocab, (table.vocab + 31) // 32
+    R = int(row_base.shape[0])
+    G = int(arena_trans.shape[0])
+    tr = arena_trans.cpu().numpy().view(np.uint16)
+    acc = arena_accept.cpu().numpy()
+    base = row_base.cpu().numpy()
+    nst = row_nstates.cpu().numpy()
+    st = row_state.cpu().numpy()
+    ps = pend_src.cpu().numpy() if pend_src is not None else None
+    toks = tokens.cpu().numpy() if tokens is not None else np.zeros(0, dtype=np.int32)
+    bb = base_bits.cpu().numpy().view(np.uint32) if base_bits is not None else None
+    bi = base_idx.cpu().numpy() if base_idx is not None and bb is not None else None
+    n_static = bb.shape[0] if bb is not None else 0
+    bits = np.zeros((n_static + R, words), dtype=np.uint32)
+    if n_static:
+        bits[:n_static] = bb
+    idx = np.full(R, -1, dtype=np.int32)
+    after = np.full(R, -1, dtype=np.int32)
+    mat, lens, eos = table.mat, table.lens, table.eos
+    has_bytes = np.flatnonzero(lens > 0)
+    for r in range(R):
+        if base[r] < 0:
+            if bi is not None:
+                idx[r] = bi[r]
+            continue
+        idx[r] = n_static + r
+        b0 = int(base[r])
+        n = max(0, min(int(nst[r]), G - b0))     # states of this guide that lie inside the arena
+        s = int(st[r]) if 0 <= int(st[r]) < n else -1
+
+        def step(states, byts):
+            nxt = tr[b0 + states, byts].astype(np.int64)
+            return np.where(nxt < n, nxt, -1)
+
+        if ps is not None and 0 <= int(ps[r]) < toks.shape[0]:
+            t = int(toks[int(ps[r])])
+            if 0 <= t < V and eos[t]:
+                pass
+            elif not 0 <= t < V or lens[t] == 0:
+                s = -1
+            else:
+                for b in mat[t, :lens[t]]:
+                    s = int(step(np.asarray([s]), np.asarray([b]))[0]) if s >= 0 else -1
+        after[r] = s
+        allowed = np.zeros(V, dtype=bool)
+        if s >= 0:
+            alive = has_bytes
+            cur = np.full(alive.shape[0], s, dtype=np.int64)
+            pos = 0
+            done = []
+            while alive.size:
+                ended = lens[alive] == pos
+                done.append(alive[ended])
+                alive, cur = alive[~ended], cur[~ended]
+                if not alive.size:
+                    break
+                cur = step(cur, mat[alive, pos])
+                keep = cur >= 0
+                alive, cur = alive[keep], cur[keep]
+                pos += 1
+            if done:
+                allowed[np.concatenate(done)] = True
+            if acc[b0 + s]:
+                allowed |= eos
+        if bi is not None and bi[r] >= 0:
+            row = bb[bi[r]]
+            allowed &= ((row[np.arange(V) >> 5] >> (np.arange(V) & 31).astype(np.uint32)) & 1).astype(bool)
+        if not allowed.any():
+            allowed[table.eos_ids[0]] = True
+        padded = np.zeros(words * 32, dtype=bool)
+        padded[:V] = allowed
+        bits[n_static + r] = np.packbits(padded, bitorder="little").view(np.uint32)
+    dev = row_base.device
+    return (torch.from_numpy(bits.view(np.int32)).to(dev), torch.from_numpy(idx).to(dev),
+            torch.from_numpy(after).to(dev))
