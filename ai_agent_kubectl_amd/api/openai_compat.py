@@ -23,13 +23,19 @@ fields, constrain the completion (engine/guided.py, csrc/guide_mask.hip): with f
 matches the pattern / is one of the choices, with "length" it is a prefix of a match.  Both together, an empty
 string or list and a cap violation get 422; a pattern outside the dialect, one the tokenizer cannot spell, a full
 guide table and a tensor-parallel engine get 400.
+JSON mode (engine/guided.py, csrc/guide_stack.hip): `response_format: {"type": "json_object"}` constrains the content
+to one RFC 8259 object, `{"type": "json_schema", "json_schema": {"name": .., "schema": {..}}}` and vLLM's
+`guided_json` (a dict or a JSON string, at most 16 KiB) to the supported subset of JSON Schema; `{"type": "text"}` is
+the default.  An unknown type, a missing or non-object schema, an oversized schema and any two of response_format,
+guided_json, guided_regex and guided_choice get 422; a schema outside the subset gets 400 like a bad pattern.
 Auth: when API_AUTH_KEY is set, `Authorization: Bearer <key>` or `X-API-Key: <key>`.
 """
 from __future__ import annotations
 
 import time
 import uuid
-from typing import Dict, List, Optional
+import json
+from typing import Any, Dict, List, Optional, Union
 
 from fastapi import Header, HTTPException, Request
 from pydantic import BaseModel, Field, field_validator, model_validator
@@ -57,6 +63,40 @@ class ChatRequest(BaseModel):
     logit_bias: Optional[Dict[str, float]] = None   # OpenAI's wire form: decimal token-id strings -> bias
     guided_regex: Optional[str] = Field(None, min_length=1, max_length=2048)
     guided_choice: Optional[List[str]] = Field(None, min_length=1, max_length=256)
+    guided_json: Optional[Union[Dict[str, Any], str]] = None
+    response_format: Optional[Dict[str, Any]] = None
+
+    @field_validator("guided_json")
+    @classmethod
+    def _guided_json_schema(cls, v):
+        if v is None:
+            return v
+        if isinstance(v, str):
+            try:
+                parsed = json.loads(v)
+            except ValueError:
+                raise ValueError("guided_json must be a JSON Schema object or its JSON text")
+            if not isinstance(parsed, dict):
+                raise ValueError("guided_json must be a JSON Schema object")
+        if len((v if isinstance(v, str) else json.dumps(v, ensure_ascii=False)).encode("utf-8")) > MAX_SCHEMA_BYTES:
+            raise ValueError(f"guided_json accepts at most {MAX_SCHEMA_BYTES} bytes of schema")
+        return v
+
+    @field_validator("response_format")
+    @classmethod
+    def _response_format_shape(cls, v):
+        if v is None:
+            return v
+        kind = v.get("type")
+        if kind not in ("text", "json_object", "json_schema"):
+            raise ValueError("response_format.type must be text, json_object or json_schema")
+        if kind == "json_schema":
+            js = v.get("json_schema")
+            if not isinstance(js, dict) or not isinstance(js.get("schema"), dict):
+                raise ValueError("response_format.json_schema.schema must be a JSON Schema object")
+            if len(json.dumps(js["schema"], ensure_ascii=False).encode("utf-8")) > MAX_SCHEMA_BYTES:
+                raise ValueError(f"response_format.json_schema.schema accepts at most {MAX_SCHEMA_BYTES} bytes")
+        return v
 
     @field_validator("guided_choice")
     @classmethod
@@ -86,8 +126,13 @@ class ChatRequest(BaseModel):
             raise ValueError("top_logprobs requires logprobs: true")
         if self.guided_regex is not None and self.guided_choice is not None:
             raise ValueError("guided_regex and guided_choice cannot be combined")
+        structured = self.response_format is not None and self.response_format.get("type") != "text"
+        if structured + (self.guided_json is not None) + (self.guided_regex is not None) + (self.guided_choice is not None) > 1:
+            raise ValueError("response_format, guided_json, guided_regex and guided_choice cannot be combined")
         return self
 
+
+MAX_SCHEMA_BYTES = 16384   # engine/guided.py MAX_SCHEMA_BYTES
 
 _NEUTRAL = dict(presence_penalty=0.0, frequency_penalty=0.0, repetition_penalty=1.0, logit_bias=None)
 
@@ -129,6 +174,13 @@ def install(app, svc, settings) -> None:
             kw["guided_regex"] = req.guided_regex
         if req.guided_choice is not None:
             kw["guided_choice"] = list(req.guided_choice)
+        if req.guided_json is not None:
+            kw["guided_json"] = req.guided_json
+        fmt = (req.response_format or {}).get("type", "text")
+        if fmt == "json_object":
+            kw["json_object"] = True
+        elif fmt == "json_schema":
+            kw["guided_json"] = req.response_format["json_schema"]["schema"]
         content = None
         try:
             if req.logprobs:

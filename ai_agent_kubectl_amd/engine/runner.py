@@ -30,7 +30,7 @@ from ..ops.autotune import tune_engine
 
 logger = logging.getLogger("app.engine")
 from ..parallel.comm import LocalComm
-from .guided import GUIDE_STATES, GuideTable, pack_guides
+from .guided import GUIDE_STATES, GuideTable, StackGuide, pack_guide_stacks, pack_guides
 from .penalties import pack_edits
 from .safe_decode import mask_index_for
 from .scheduler import Batch
@@ -175,6 +175,9 @@ class ModelRunner:
         self._guide_lock = threading.Lock()
         self._h_gds: List[Optional[torch.Tensor]] = [None, None]
         self._gflip = 0
+        # ... and the stack image of a step with a row under a stack guide (JSON mode, _stage_guide_stacks)
+        self._h_gss: List[Optional[torch.Tensor]] = [None, None]
+        self._sflip = 0
         # the records of the step read back last (collect / execute), for engine._settle to take
         self.last_logprobs: Optional[StepLogprobs] = None
         self.d_hdr = torch.zeros(HDR, dtype=torch.int32, device=self.device)
@@ -194,7 +197,7 @@ class ModelRunner:
         self.graph_pool = None
         self.stats = {"decode_steps": 0, "prefill_steps": 0, "graph_replays": 0, "decode_ms": 0.0,
                       "prefill_ms": 0.0, "prefill_tokens": 0, "persistent_stalls": 0, "sampled_steps": 0,
-                      "logprob_steps": 0, "penalty_steps": 0, "guided_steps": 0}
+                      "logprob_steps": 0, "penalty_steps": 0, "guided_steps": 0, "json_steps": 0}
         # bucket -> the captured graph holds the persistent decode kernel (its error word must be read
         # back on every replay of that graph, whatever model.persistent says now)
         self.graph_persistent: Dict[int, bool] = {}
@@ -309,7 +312,26 @@ class ModelRunner:
                 self._h_gds[k] = hb
             hb.numpy()[:n] = img
             dimg = hb[:n].to(self.device, non_blocking=True)
-        return GuideArrays.from_image(dimg, rows, self.token_table, table.trans, table.accept, self.d_out)
+        arrays = GuideArrays.from_image(dimg, rows, self.token_table, table.trans, table.accept, self.d_out)
+        if any(isinstance(s.params.guide, StackGuide) and s.guide_ref is not None for s in batch.seqs):
+            self.stats["json_steps"] += 1
+            arrays.with_stacks(self._stage_guide_stacks(batch, rows), rows, table.arena_pop)
+        return arrays
+
+    def _stage_guide_stacks(self, batch: Batch, rows: int) -> torch.Tensor:
+        """The step's stack image (engine/guided.py pack_guide_stacks) -> device, by the route of _stage_guides:
+        one of two pinned buffers, no host sync.  Only a step with a row under a stack guide comes here."""
+        img = pack_guide_stacks(batch.seqs, rows, self.tokenizer)
+        if self.device.type != "cuda":
+            return torch.from_numpy(img)
+        n = img.shape[0]
+        k = self._sflip = self._sflip ^ 1
+        hb = self._h_gss[k]
+        if hb is None or hb.numel() < n:
+            hb = torch.empty(max(n, 10 * self.bmax), dtype=torch.int32, pin_memory=True)
+            self._h_gss[k] = hb
+        hb.numpy()[:n] = img
+        return hb[:n].to(self.device, non_blocking=True)
 
     def _stage_edits(self, batch: Batch, rows: int, pend: Optional[List[int]]) -> LogitEdits:
         """The step's penalty / logit_bias image (engine/penalties.py pack_edits) -> device without a host

@@ -13,6 +13,7 @@ from __future__ import annotations
 import asyncio
 import collections
 import concurrent.futures
+import json
 import logging
 import threading
 from typing import List, Optional
@@ -133,7 +134,8 @@ class EngineLLM(LLMBackend):
         penalties: presence_penalty, frequency_penalty, repetition_penalty, logit_bias ({token id: bias}),
         applied to the logits before the token is chosen, also at temperature 0 (SamplingParams); and
         guided_regex or guided_choice: the completion then matches the pattern / is one of the choices when it
-        ends with "stop", and is a prefix of a match when max_tokens cuts it (engine/guided.py).
+        ends with "stop", and is a prefix of a match when max_tokens cuts it (engine/guided.py); json_object=True
+        (any JSON object) or guided_json (a JSON Schema of the supported subset, dict or string): JSON mode.
         Raises ValueError for a request the engine cannot serve (temperature > 0, penalties or a guide under
         TP > 1, a logit_bias id outside the vocabulary, a pattern outside the dialect or that the tokenizer
         cannot spell, a full guide table)."""
@@ -171,16 +173,23 @@ class EngineLLM(LLMBackend):
 
     GUIDE_CACHE = 64
 
-    def compile_guide(self, guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None):
+    def compile_guide(self, guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None,
+                      guided_json=None, json_object: bool = False):
         """The compiled guide of a request (engine/guided.py), from an LRU of the last GUIDE_CACHE sources; the
         first guided request also builds the engine's token table and guide arena here.  Host work that the
         compiler's caps and work budget keep to a fraction of a second (the token table: once per engine):
         `_chat` runs it on a worker thread, off the event loop and off the engine's loop.  Requests that arrive
         with a source that is being compiled wait for that compilation.  Raises ValueError for a pattern
         outside the dialect or past a cap."""
-        if guided_regex is not None and guided_choice is not None:
-            raise ValueError("guided_regex and guided_choice cannot be combined")
-        key = ("regex", guided_regex) if guided_regex is not None else ("choice", tuple(guided_choice))
+        if (guided_regex is not None) + (guided_choice is not None) + (guided_json is not None) + bool(json_object) > 1:
+            raise ValueError("guided_regex, guided_choice, guided_json and response_format cannot be combined")
+        if guided_json is not None and not isinstance(guided_json, str):
+            try:
+                guided_json = json.dumps(guided_json, ensure_ascii=False, allow_nan=False)   # key order kept: it is the members' order
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"guided_json: the schema is not JSON ({e})") from None
+        key = (("regex", guided_regex) if guided_regex is not None else ("json_object",) if json_object
+               else ("json", guided_json) if guided_json is not None else ("choice", tuple(guided_choice)))
         with self._guides_lock:
             g = self._guides.get(key)
             if g is not None:
@@ -194,6 +203,8 @@ class EngineLLM(LLMBackend):
             return fut.result()
         try:
             g = (guided.compile_regex(guided_regex) if guided_regex is not None
+                 else guided.compile_json_object() if json_object
+                 else guided.compile_json_schema(guided_json) if guided_json is not None
                  else guided.compile_choice(list(guided_choice)))
             if self.engine.runner.tp_size == 1:   # a TP engine refuses the request at submit: nothing to build
                 self.engine.runner.guides()
@@ -213,14 +224,16 @@ class EngineLLM(LLMBackend):
 
     async def _chat(self, messages, max_tokens, safe, temperature, top_p, top_k, seed, logprobs,
                     presence_penalty: float = 0.0, frequency_penalty: float = 0.0, repetition_penalty: float = 1.0,
-                    logit_bias=None, guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None):
+                    logit_bias=None, guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None,
+                    guided_json=None, json_object: bool = False):
         """Submit one chat request and wait for it -> (finished sequence, prompt tokens)."""
         if not self._started:
             await self.start()
         loop = asyncio.get_running_loop()
         guide = None
-        if guided_regex is not None or guided_choice is not None:
-            guide = await loop.run_in_executor(None, self.compile_guide, guided_regex, guided_choice)
+        if guided_regex is not None or guided_choice is not None or guided_json is not None or json_object:
+            guide = await loop.run_in_executor(None, self.compile_guide, guided_regex, guided_choice, guided_json,
+                                               json_object)
         fut: asyncio.Future = loop.create_future()
         params = SamplingParams(max_new_tokens=max_tokens, ignore_eos=False, safe_decode=safe,
                                 temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=seed,

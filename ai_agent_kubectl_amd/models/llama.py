@@ -101,6 +101,20 @@ class GuideArrays:
     pend_src: torch.Tensor             # int32 [S]: >= 0: the row's newest output token is tokens[pend_src], not walked yet
     tokens: torch.Tensor               # int32: the runner's d_out
     state_after: Optional[torch.Tensor] = None   # set by LlamaModel.sample: the state each row's mask was built from
+    # a step with a row under a stack guide (JSON mode, ops.guide_mask_stack); None in every other step
+    arena_pop: Optional[torch.Tensor] = None     # int16 [GUIDE_STATES, 16]
+    row_kind: Optional[torch.Tensor] = None      # int32 [S]: 1 = a stack row
+    row_depth: Optional[torch.Tensor] = None     # int32 [S]
+    row_stack: Optional[torch.Tensor] = None     # int32 [S, 8]
+    depth_after: Optional[torch.Tensor] = None   # set by LlamaModel.sample beside state_after
+    stack_after: Optional[torch.Tensor] = None
+
+    def with_stacks(self, img: torch.Tensor, rows: int, arena_pop: torch.Tensor) -> "GuideArrays":
+        """Views of a packed int32 image [kind | depth | stack words] (rows, rows, 8 * rows)."""
+        self.arena_pop = arena_pop
+        self.row_kind, self.row_depth = img[:rows], img[rows:2 * rows]
+        self.row_stack = img[2 * rows:10 * rows].view(rows, 8)
+        return self
 
     @classmethod
     def from_image(cls, img: torch.Tensor, rows: int, table, arena_trans, arena_accept, tokens) -> "GuideArrays":
@@ -405,7 +419,12 @@ class LlamaModel:
             if self.tp_size != 1:
                 raise RuntimeError("sampling with temperature > 0 is not wired through the TP worker protocol")
             gd = samp.guide
-            if gd is not None:
+            if gd is not None and gd.row_kind is not None:   # a row under a stack guide (JSON mode)
+                mask_bits, mask_idx, gd.state_after, gd.depth_after, gd.stack_after = ops.guide_mask_stack(
+                    gd.table, gd.arena_trans, gd.arena_accept, gd.arena_pop, gd.row_base, gd.row_nstates, gd.row_state,
+                    gd.row_kind, gd.row_depth, gd.row_stack, gd.pend_src, gd.tokens, mask_bits,
+                    mask_idx if mask_bits is not None else None)
+            elif gd is not None:
                 mask_bits, mask_idx, gd.state_after = ops.guide_mask(
                     gd.table, gd.arena_trans, gd.arena_accept, gd.row_base, gd.row_nstates, gd.row_state, gd.pend_src,
                     gd.tokens, mask_bits, mask_idx if mask_bits is not None else None)

@@ -548,6 +548,69 @@ def guide_mask(table: TokenTable, arena_trans: torch.Tensor, arena_accept: torch
     return bits, idx, after
 
 
+def guide_mask_stack(table: TokenTable, arena_trans: torch.Tensor, arena_accept: torch.Tensor, arena_pop: torch.Tensor,
+                     row_base: torch.Tensor, row_nstates: torch.Tensor, row_state: torch.Tensor,
+                     row_kind: torch.Tensor, row_depth: torch.Tensor, row_stack: torch.Tensor,
+                     pend_src: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None,
+                     base_bits: Optional[torch.Tensor] = None, base_idx: Optional[torch.Tensor] = None):
+    """guide_mask for a step with rows under a stack guide (JSON mode; csrc/guide_stack.hip; semantics:
+    ops/reference.py `guide_mask_stack`).  guide_mask's arguments, plus arena_pop int16 [G, 16] (row `base` of a
+    guide's range holds its pop_to), row_kind int32 [R] (0: a DFA row, 1: a stack row), row_depth int32 [R] and
+    row_stack int32 [R, 8] (64 four-bit symbols, bottom first, symbol i in bits 4 (i mod 8) of word i / 8).
+    -> (bits, idx, state_after, depth_after int32 [R], stack_after int32 [R, 8]): the last three describe each
+    row after its pending token, which is what its mask was built from."""
+    if _ref(row_base):
+        return ref.guide_mask_stack(table, arena_trans, arena_accept, arena_pop, row_base, row_nstates, row_state,
+                                    row_kind, row_depth, row_stack, pend_src, tokens, base_bits, base_idx)
+    lib = require()
+    dev = row_base.device
+    R = row_base.numel()
+    words = (table.vocab + 31) // 32
+    per_row = [row_base, row_nstates, row_state, row_kind, row_depth] + ([pend_src] if pend_src is not None else []) \
+        + ([base_idx] if base_idx is not None else [])
+    for t in per_row + ([tokens] if tokens is not None else []):
+        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f"guide_mask_stack: every per-row array must be a contiguous 1-d int32 tensor on {dev}")
+    if any(t.numel() != R for t in per_row):
+        raise ValueError("guide_mask_stack: row_base, row_nstates, row_state, row_kind, row_depth, pend_src and "
+                         "base_idx are [rows]")
+    if row_stack.dtype != torch.int32 or row_stack.shape != (R, 8) or row_stack.device != dev \
+            or not row_stack.is_contiguous():
+        raise ValueError(f"guide_mask_stack: row_stack must be contiguous int32 [rows, 8] on {dev}")
+    if (pend_src is None) != (tokens is None):
+        raise ValueError("guide_mask_stack: pend_src [rows] and tokens come together")
+    G = arena_trans.shape[0] if arena_trans.dim() == 2 else -1
+    if arena_trans.dtype != torch.int16 or arena_trans.dim() != 2 or arena_trans.shape[1] != 256 \
+            or not arena_trans.is_contiguous() or arena_trans.device != dev or arena_accept.dtype != torch.uint8 \
+            or arena_accept.shape != (G,) or arena_accept.device != dev or not arena_accept.is_contiguous() \
+            or arena_pop.dtype != torch.int16 or arena_pop.shape != (G, 16) or arena_pop.device != dev \
+            or not arena_pop.is_contiguous():
+        raise ValueError(f"guide_mask_stack: the arena is int16 [states, 256] with uint8 [states] accept flags and "
+                         f"int16 [states, 16] pop tables on {dev}")
+    if table.rec.device != dev:
+        raise ValueError(f"guide_mask_stack: the token table lives on {table.rec.device}, the rows on {dev}")
+    n_static = 0
+    if base_bits is not None:
+        if base_bits.dtype != torch.int32 or base_bits.dim() != 2 or base_bits.shape[1] != words \
+                or base_bits.device != dev or not base_bits.is_contiguous() or base_idx is None:
+            raise ValueError(f"guide_mask_stack: base_bits must be contiguous int32 [rows of masks, {words}] with base_idx")
+        n_static = base_bits.shape[0]
+    bits = torch.empty((n_static + R, words), dtype=torch.int32, device=dev)
+    if n_static:
+        bits[:n_static].copy_(base_bits)
+    idx = torch.empty(R, dtype=torch.int32, device=dev)
+    after = torch.empty(R, dtype=torch.int32, device=dev)
+    depth_after = torch.empty(R, dtype=torch.int32, device=dev)
+    stack_after = torch.empty((R, 8), dtype=torch.int32, device=dev)
+    check(lib.ka_guide_mask_stack(
+        _p(bits), _p(idx), _p(after), _p(depth_after), _p(stack_after), _p(table.rec),
+        _p(table.ovf) if table.ovf_bytes else None, table.ovf_bytes, table.vocab, table.eos_ids[0], _p(arena_trans),
+        _p(arena_accept), _p(arena_pop), G, _p(row_base), _p(row_nstates), _p(row_state), _p(row_kind), _p(row_depth),
+        _p(row_stack), _p(pend_src), _p(tokens), tokens.numel() if tokens is not None else 0, _p(base_bits),
+        _p(base_idx) if base_bits is not None else None, n_static, R, _stream()), "guide_mask_stack")
+    return bits, idx, after, depth_after, stack_after
+
+
 def argmax_combine(vals: torch.Tensor, idxs: torch.Tensor) -> torch.Tensor:
     """TP vocab-parallel greedy combine: vals / idxs [ranks, S] (every rank's best value and global token
     id) -> [S] int32 id of the largest value, the lowest id on ties (csrc/sampling.hip)."""

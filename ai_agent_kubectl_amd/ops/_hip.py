@@ -63,6 +63,8 @@ _SIGS = {
     "ka_logit_adjust_threads": [],
     "ka_guide_mask": [P, P, P, P, P, I, I, I, P, P, I, P, P, P, P, P, I, P, P, I, I, P],
     "ka_guide_mask_tile": [],
+    "ka_guide_mask_stack": [P, P, P, P, P, P, P, I, I, I, P, P, P, I, P, P, P, P, P, P, P, P, I, P, P, I, I, P],
+    "ka_guide_mask_stack_tile": [],
     "ka_moe_topk": [P, P, P, I, I, I, P],
     "ka_paged_decode": [P, P, P, P, P, I, P, I, I, I, I, I, F, P],
     "ka_paged_decode_rope": [P, P, P, I, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, P],

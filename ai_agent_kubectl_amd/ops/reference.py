@@ -510,3 +510,164 @@ def guide_mask(table, arena_trans, arena_accept, row_base, row_nstates, row_stat
     dev = row_base.device
     return (torch.from_numpy(bits.view(np.int32)).to(dev), torch.from_numpy(idx).to(dev),
             torch.from_numpy(after).to(dev))
+
+
+def _stack_words(stack):
+    """uint32 [8]: the symbols, bottom first, symbol i in bits 4 (i mod 8) of word i / 8."""
+    import numpy as np
+    w = np.zeros(8, dtype=np.uint32)
+    for i, y in enumerate(stack):
+        w[i >> 3] |= np.uint32(int(y) << (4 * (i & 7)))
+    return w
+
+
+def guide_mask_stack(table, arena_trans, arena_accept, arena_pop, row_base, row_nstates, row_state, row_kind,
+                     row_depth, row_stack, pend_src, tokens, base_bits, base_idx):
+    """The definition of ops.guide_mask_stack (csrc/guide_stack.hip): guide_mask for a step with rows under a
+    stack guide (engine/guided.py StackGuide, JSON mode).
+
+    As guide_mask, plus arena_pop int16 [G, 16] (row `base` of a guide's range: its pop_to, uint16 patterns),
+    row_kind int32 [R] (0: a DFA row, exactly guide_mask's entry semantics; 1: a stack row), row_depth int32 [R]
+    and row_stack int32 [R, 8] (64 four-bit symbols, bottom first, symbol i in bits 4 (i mod 8) of word i / 8).
+    A stack row whose depth is outside 0..64 or that holds a symbol 0 or 15 below its depth is dead.
+
+    An entry e of a stack row, in a state s inside [0, n): 0xFFFF dead.  Bit 15 set: a pop; push bits 11-14
+    that are not 0, or an empty stack: dead; else the top symbol y is taken and the next state is pop_to[y]
+    (not below n: dead).  Bit 15 clear: the next state is bits 0-10 (not below n: dead); push bits y that are
+    not 0 push y: y = 15, a stack that already holds 64 symbols, or 16 symbols that THIS token pushed and that
+    are still on the stack: dead.  Every token starts from the row's stack after the pending token.
+    -> (bits, idx, state_after) as guide_mask, depth_after int32 [R], stack_after int32 [R, 8]: the row after
+    its pending token (what the mask was built from); 0 for a row that is dead, not guided or of kind 0."""
+    import numpy as np
+    V, words = table.vocab, (table.vocab + 31) // 32
+    R = int(row_base.shape[0])
+    G = int(arena_trans.shape[0])
+    tr = arena_trans.cpu().numpy().view(np.uint16)
+    acc = arena_accept.cpu().numpy()
+    apop = arena_pop.cpu().numpy().view(np.uint16)
+    base = row_base.cpu().numpy()
+    nst = row_nstates.cpu().numpy()
+    st = row_state.cpu().numpy()
+    kind = row_kind.cpu().numpy()
+    dep = row_depth.cpu().numpy()
+    stk = row_stack.cpu().numpy().view(np.uint32).reshape(R, 8)
+    ps = pend_src.cpu().numpy() if pend_src is not None else None
+    toks = tokens.cpu().numpy() if tokens is not None else np.zeros(0, dtype=np.int32)
+    bb = base_bits.cpu().numpy().view(np.uint32) if base_bits is not None else None
+    bi = base_idx.cpu().numpy() if base_idx is not None and bb is not None else None
+    n_static = bb.shape[0] if bb is not None else 0
+    bits = np.zeros((n_static + R, words), dtype=np.uint32)
+    if n_static:
+        bits[:n_static] = bb
+    idx = np.full(R, -1, dtype=np.int32)
+    after = np.full(R, -1, dtype=np.int32)
+    depth_after = np.zeros(R, dtype=np.int32)
+    stack_after = np.zeros((R, 8), dtype=np.uint32)
+    mat, lens, eos = table.mat, table.lens, table.eos
+    has_bytes = np.flatnonzero(lens > 0)
+    for r in range(R):
+        if base[r] < 0:
+            if bi is not None:
+                idx[r] = bi[r]
+            continue
+        idx[r] = n_static + r
+        b0 = int(base[r])
+        n = max(0, min(int(nst[r]), G - b0))     # states of this guide that lie inside the arena
+        s = int(st[r]) if 0 <= int(st[r]) < n else -1
+        stacked = int(kind[r]) == 1
+        popto = apop[b0].astype(np.int64) if stacked and b0 < G else np.full(16, 0xFFFF, dtype=np.int64)
+        row = []                                 # the row's stack, bottom first
+        if stacked:
+            d = int(dep[r])
+            if 0 <= d <= 64:
+                row = [(int(stk[r, i >> 3]) >> (4 * (i & 7))) & 15 for i in range(d)]
+            if not 0 <= d <= 64 or any(y in (0, 15) for y in row):
+                s, row = -1, []
+
+        # one byte for every token of `cur` (states), `reg` (the symbols each token pushed, newest in the low
+        # four bits), `cnt` (how many of them) and `cons` (symbols each took from the row's stack `rowsym`)
+        def step(cur, reg, cnt, cons, byts, rowsym):
+            e = tr[b0 + cur, byts].astype(np.int64)
+            if not stacked:
+                return np.where(e < n, e, -1), reg, cnt, cons
+            y = (e >> 11) & 15
+            is_pop = (e & 0x8000) != 0
+            tgt = e & 0x7FF
+            depth = len(rowsym) - cons + cnt
+            go = ~is_pop & (tgt < n) & (y != 15)
+            push = go & (y > 0)
+            go &= ~push | ((depth < 64) & (cnt < 16))
+            push &= go
+            pop = is_pop & (y == 0) & (depth > 0)
+            from_reg = pop & (cnt > 0)
+            from_row = pop & (cnt == 0)
+            padded = np.asarray(list(rowsym) + [0], dtype=np.int64)
+            sym = np.where(from_reg, (reg & np.uint64(15)).astype(np.int64),
+                           padded[np.clip(len(rowsym) - 1 - cons, -1, len(rowsym) - 1)])
+            sym = np.where(pop, sym, 0)
+            to = popto[sym]
+            pop &= (sym >= 1) & (sym <= 14) & (to < n)
+            from_reg &= pop
+            from_row &= pop
+            nxt = np.where(go, tgt, np.where(pop, to, -1))
+            reg = np.where(push, (reg << np.uint64(4)) | y.astype(np.uint64), np.where(from_reg, reg >> np.uint64(4), reg))
+            return nxt, reg, cnt + push - from_reg, cons + from_row
+
+        if ps is not None and 0 <= int(ps[r]) < toks.shape[0]:
+            t = int(toks[int(ps[r])])
+            if 0 <= t < V and eos[t]:
+                pass
+            elif not 0 <= t < V or lens[t] == 0:
+                s = -1
+            elif s >= 0:
+                cur, reg = np.asarray([s], dtype=np.int64), np.zeros(1, dtype=np.uint64)
+                cnt, cons = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+                for b in mat[t, :lens[t]]:
+                    cur, reg, cnt, cons = step(cur, reg, cnt, cons, np.asarray([b]), row)
+                    if cur[0] < 0:
+                        break
+                s = int(cur[0])
+                if s >= 0 and stacked:           # the token's own symbols go on top of what it left of the row's
+                    own = [(int(reg[0]) >> (4 * i)) & 15 for i in range(int(cnt[0]))][::-1]
+                    row = row[:len(row) - int(cons[0])] + own
+        if s < 0:
+            row = []
+        after[r] = s
+        if stacked:
+            depth_after[r] = len(row)
+            stack_after[r] = _stack_words(row)
+        allowed = np.zeros(V, dtype=bool)
+        if s >= 0:
+            alive = has_bytes
+            m = alive.shape[0]
+            cur, reg = np.full(m, s, dtype=np.int64), np.zeros(m, dtype=np.uint64)
+            cnt, cons = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
+            pos = 0
+            done = []
+            while alive.size:
+                ended = lens[alive] == pos
+                done.append(alive[ended])
+                keep = ~ended
+                alive, cur, reg, cnt, cons = alive[keep], cur[keep], reg[keep], cnt[keep], cons[keep]
+                if not alive.size:
+                    break
+                cur, reg, cnt, cons = step(cur, reg, cnt, cons, mat[alive, pos], row)
+                keep = cur >= 0
+                alive, cur, reg, cnt, cons = alive[keep], cur[keep], reg[keep], cnt[keep], cons[keep]
+                pos += 1
+            if done:
+                allowed[np.concatenate(done)] = True
+            if acc[b0 + s]:
+                allowed |= eos
+        if bi is not None and bi[r] >= 0:
+            brow = bb[bi[r]]
+            allowed &= ((brow[np.arange(V) >> 5] >> (np.arange(V) & 31).astype(np.uint32)) & 1).astype(bool)
+        if not allowed.any():
+            allowed[table.eos_ids[0]] = True
+        padded = np.zeros(words * 32, dtype=bool)
+        padded[:V] = allowed
+        bits[n_static + r] = np.packbits(padded, bitorder="little").view(np.uint32)
+    dev = row_base.device
+    return (torch.from_numpy(bits.view(np.int32)).to(dev), torch.from_numpy(idx).to(dev),
+            torch.from_numpy(after).to(dev), torch.from_numpy(depth_after).to(dev),
+            torch.from_numpy(stack_after.view(np.int32)).to(dev))
