@@ -28,6 +28,19 @@ to one RFC 8259 object, `{"type": "json_schema", "json_schema": {"name": .., "sc
 `guided_json` (a dict or a JSON string, at most 16 KiB) to the supported subset of JSON Schema; `{"type": "text"}` is
 the default.  An unknown type, a missing or non-object schema, an oversized schema and any two of response_format,
 guided_json, guided_regex and guided_choice get 422; a schema outside the subset gets 400 like a bad pattern.
+`stop` (a string or a list of 1..4 strings, each 1..64 bytes of UTF-8; anything else gets 422) ends the completion
+before the first of them that occurs in it, with finish_reason "stop" (engine/streaming.py); it combines with every
+other field.  A request that sent `stop` also gets vLLM's `choices[0].stop_reason`: the matched string, or null for
+EOS or length.
+`stream: true` answers with server-sent events (`text/event-stream`): chunks of `object: "chat.completion.chunk"`
+that share `id`, `created` and `model`; the first one's delta is {"role": "assistant", "content": ""}, then content
+chunks (with `logprobs: {"content": [...]}` when asked: an entry leaves with the first byte of its token), then one
+with `delta: {}` and the `finish_reason` (and `stop_reason` under the rule above), then `data: [DONE]`.  With
+`stream_options: {"include_usage": true}` a last chunk with `choices: []` and `usage` comes before [DONE] and every
+other chunk carries `"usage": null`; `stream_options` without `stream` gets 422.  The deltas join to exactly the
+content, and the entries to exactly the logprobs, of the same request without `stream`.  What fails before the
+first byte (422, 400, 503) is a plain HTTP error; a failure afterwards is one `data: {"error": {...}}` event and the
+stream ends without [DONE].  A client that disconnects aborts its request.
 Auth: when API_AUTH_KEY is set, `Authorization: Bearer <key>` or `X-API-Key: <key>`.
 """
 from __future__ import annotations
@@ -38,7 +51,10 @@ import json
 from typing import Any, Dict, List, Optional, Union
 
 from fastapi import Header, HTTPException, Request
+from fastapi.responses import StreamingResponse
 from pydantic import BaseModel, Field, field_validator, model_validator
+
+from ..llm.base import LLMUnavailableError
 
 
 class ChatMessage(BaseModel):
@@ -65,6 +81,25 @@ class ChatRequest(BaseModel):
     guided_choice: Optional[List[str]] = Field(None, min_length=1, max_length=256)
     guided_json: Optional[Union[Dict[str, Any], str]] = None
     response_format: Optional[Dict[str, Any]] = None
+    stop: Optional[Union[str, List[str]]] = None
+    stream_options: Optional[Dict[str, Any]] = None
+
+    @field_validator("stop")
+    @classmethod
+    def _stop_entries(cls, v):
+        if v is None:
+            return v
+        stops = [v] if isinstance(v, str) else v
+        if not 1 <= len(stops) <= 4:
+            raise ValueError("stop accepts a string or 1..4 strings")
+        for s in stops:
+            try:
+                n = len(s.encode("utf-8"))
+            except UnicodeEncodeError:
+                raise ValueError("every stop string must be UTF-8") from None
+            if not 1 <= n <= 64:
+                raise ValueError("every stop string must be 1..64 bytes long")
+        return stops
 
     @field_validator("guided_json")
     @classmethod
@@ -124,6 +159,8 @@ class ChatRequest(BaseModel):
     def _top_logprobs_needs_logprobs(self):
         if self.top_logprobs is not None and not self.logprobs:
             raise ValueError("top_logprobs requires logprobs: true")
+        if self.stream_options is not None and not self.stream:
+            raise ValueError("stream_options requires stream: true")
         if self.guided_regex is not None and self.guided_choice is not None:
             raise ValueError("guided_regex and guided_choice cannot be combined")
         structured = self.response_format is not None and self.response_format.get("type") != "text"
@@ -155,12 +192,61 @@ def install(app, svc, settings) -> None:
         _auth(authorization, x_api_key)
         return {"object": "list", "data": [{"id": settings.MODEL, "object": "model", "owned_by": "local"}]}
 
+    async def _stream(req: ChatRequest, request: Request, msgs, kw, head):
+        """`stream: true`.  The backend's first event is awaited before the response starts, so a request that the
+        engine refuses is a plain 400 / 503."""
+        if not hasattr(backend, "stream_chat"):
+            raise HTTPException(status_code=400, detail="this backend does not stream")
+        kw.pop("with_stop", None)
+        events = backend.stream_chat(msgs, top_logprobs=(req.top_logprobs or 0) if req.logprobs else None, **kw)
+        try:
+            first = await events.__anext__()
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        except LLMUnavailableError as e:
+            raise HTTPException(status_code=503, detail=str(e))
+        usage = bool((req.stream_options or {}).get("include_usage"))
+
+        def chunk(choices, **extra) -> bytes:
+            body = dict(head, object="chat.completion.chunk", choices=choices, **extra)
+            if usage and "usage" not in body:
+                body["usage"] = None
+            return b"data: " + json.dumps(body, ensure_ascii=False).encode("utf-8", "replace") + b"\n\n"
+
+        async def body():
+            try:
+                yield chunk([{"index": 0, "delta": {"role": "assistant", "content": ""}, "finish_reason": None}])
+                n_out = 0
+                async for ev in events:
+                    if "finish_reason" in ev:
+                        last = {"index": 0, "delta": {}, "finish_reason": ev["finish_reason"]}
+                        if req.stop is not None:
+                            at = ev["stop_reason"]
+                            last["stop_reason"] = req.stop[at] if at is not None else None
+                        n_out = ev["completion_tokens"]
+                        yield chunk([last])
+                        continue
+                    ch = {"index": 0, "delta": {"content": ev["text"]}, "finish_reason": None}
+                    if ev["logprobs"] is not None:
+                        ch["logprobs"] = {"content": ev["logprobs"]}
+                    yield chunk([ch])
+                if usage:
+                    n_in = first["prompt_tokens"]
+                    yield chunk([], usage={"prompt_tokens": n_in, "completion_tokens": n_out,
+                                           "total_tokens": n_in + n_out})
+                yield b"data: [DONE]\n\n"
+            except Exception as e:   # after the first byte: one error event, and no [DONE]
+                kind = "service_unavailable" if isinstance(e, LLMUnavailableError) else "internal_error"
+                yield b"data: " + json.dumps({"error": {"message": str(e), "type": kind}}).encode() + b"\n\n"
+            finally:
+                await events.aclose()   # a client that went away: the backend aborts the request
+
+        return StreamingResponse(body(), media_type="text/event-stream", headers={"Cache-Control": "no-cache"})
+
     @app.post("/v1/chat/completions")
     async def chat_completions(req: ChatRequest, request: Request, authorization: Optional[str] = Header(None),
                                x_api_key: Optional[str] = Header(None)):
         _auth(authorization, x_api_key)
-        if req.stream:
-            raise HTTPException(status_code=400, detail="stream=true is not supported")
         msgs = [m.model_dump() for m in req.messages]
         kw = dict(max_tokens=req.max_tokens or 64, temperature=req.temperature or 0.0,
                   top_p=1.0 if req.top_p is None else req.top_p, top_k=req.top_k or 0, seed=req.seed)
@@ -181,23 +267,33 @@ def install(app, svc, settings) -> None:
             kw["json_object"] = True
         elif fmt == "json_schema":
             kw["guided_json"] = req.response_format["json_schema"]["schema"]
-        content = None
+        if req.stop is not None:   # only when sent, like the penalties
+            kw.update(stop=[s.encode("utf-8") for s in req.stop], with_stop=True)
+        head = {"id": "chatcmpl-" + uuid.uuid4().hex[:24], "created": int(time.time()),
+                "model": req.model or settings.MODEL}
+        if req.stream:
+            return await _stream(req, request, msgs, kw, head)
+        content, matched = None, None
         try:
             if req.logprobs:
                 if not hasattr(backend, "generate_chat_logprobs"):
                     raise ValueError("this backend does not report logprobs")
-                text, finish, n_in, n_out, content = await backend.generate_chat_logprobs(
+                text, finish, n_in, n_out, content, *matched = await backend.generate_chat_logprobs(
                     msgs, top_logprobs=req.top_logprobs or 0, **kw)
             else:
-                text, finish, n_in, n_out = await backend.generate_chat(msgs, **kw)
+                text, finish, n_in, n_out, *matched = await backend.generate_chat(msgs, **kw)
         except ValueError as e:   # a request this engine cannot serve (sampling / logprobs / penalties / guides under TP > 1, a bad pattern)
             raise HTTPException(status_code=400, detail=str(e))
+        except LLMUnavailableError as e:
+            raise HTTPException(status_code=503, detail=str(e))
         choice = {"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": finish}
         if content is not None:   # only when asked for: the response is otherwise what it always was
             choice["logprobs"] = {"content": content}
+        if req.stop is not None:
+            choice["stop_reason"] = req.stop[matched[0]] if matched[0] is not None else None
         return {
-            "id": "chatcmpl-" + uuid.uuid4().hex[:24], "object": "chat.completion", "created": int(time.time()),
-            "model": req.model or settings.MODEL,
+            "id": head["id"], "object": "chat.completion", "created": head["created"],
+            "model": head["model"],
             "choices": [choice],
             "usage": {"prompt_tokens": n_in, "completion_tokens": n_out, "total_tokens": n_in + n_out},
         }

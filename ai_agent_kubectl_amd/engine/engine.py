@@ -36,6 +36,7 @@ from .block_manager import make_block_manager
 from .runner import CollectiveTimeout, ModelRunner
 from .scheduler import Scheduler
 from .sequence import PLACEHOLDER, SamplingParams, Sequence, SeqStatus, TokenLogprob
+from .streaming import StopScanner, validate_stops
 
 logger = logging.getLogger("app.engine")
 
@@ -158,7 +159,8 @@ class LLMEngine:
             pass
 
     def submit(self, prompt_ids: List[int], params: SamplingParams, callback: Callable[[Sequence], None],
-               forced_prefix: Optional[List[int]] = None) -> Sequence:
+               forced_prefix: Optional[List[int]] = None,
+               on_tokens: Optional[Callable[[Sequence, int], None]] = None) -> Sequence:
         if params.temperature > 0 and self.runner.tp_size > 1:
             # the vocab-parallel combine of sampled scores needs the per-row arrays on every rank: a
             # worker-protocol change that is not made yet
@@ -169,6 +171,7 @@ class LLMEngine:
             if self.runner.tp_size > 1:
                 # the logits are vocab-parallel: the ranks' (max, mass) pairs would have to be combined
                 raise ValueError("logprobs are not supported with tensor parallelism (TP > 1)")
+        validate_stops(params.stop)
         penalties.validate(params, self.runner.cfg.vocab_size, self.runner.tp_size)
         guided.validate(params, self.tokenizer, self.runner.tp_size, forced_prefix)
         # a guided request holds its guide's range of the device arena from here until it leaves (_finish,
@@ -177,6 +180,7 @@ class LLMEngine:
         seq = Sequence(prompt_ids=list(prompt_ids), params=params, callback=callback,
                        forced_prefix=list(forced_prefix or []))
         seq.guide_ref = ref
+        seq.on_tokens = on_tokens
         self._inbox.put(("add", seq))
         self._wake.set()
         return seq
@@ -383,10 +387,28 @@ class LLMEngine:
                         m.llm_ttft.observe(now - s.t_arrival)
                         m.llm_queue_wait.observe((s.t_scheduled or now) - s.t_arrival)
             eos = (not s.params.ignore_eos) and self.tokenizer.is_eos(int(tok))
+            if s.params.stop is not None and not eos:   # EOS first: it has no bytes
+                eos = self._stop_hit(s, int(tok))
+            if s.on_tokens is not None:
+                s.on_tokens(s, len(s.output_ids) - 1)
             if eos or s.num_generated >= s.params.max_new_tokens:
                 if m is not None and s.t_first_token is not None and s.num_generated > 1:
                     m.llm_tpot.observe((now - s.t_first_token) / (s.num_generated - 1))
                 self._finish(s, SeqStatus.FINISHED, "stop" if eos else "length")
+
+    def _stop_hit(self, s: Sequence, tok: int) -> bool:
+        """The bytes of the token just settled complete one of `s.params.stop`: sets `stop_cut` / `stop_match`.  The
+        sequence then finishes like an EOS one (a successor row already queued for it is discarded the same way)."""
+        sc = s.stop_scan
+        if sc is None:   # first settled token: the jump-forward prefix is output too
+            sc = s.stop_scan = StopScanner(s.params.stop)
+            for t in s.output_ids[:-1]:
+                sc.feed(self.tokenizer.token_bytes(t))
+        hit = sc.feed(self.tokenizer.token_bytes(tok))
+        if hit is None:
+            return False
+        s.stop_cut, s.stop_match = hit
+        return True
 
     # ---- lookahead: the next step scheduled and queued before the in-flight one is read back ----
     def _provisional(self, batch) -> None:

@@ -46,6 +46,10 @@ class SamplingParams:
     # guided decoding (csrc/guide_mask.hip): a compiled engine/guided.py Guide (compile_regex / compile_choice);
     # every step's token mask then also admits only tokens that keep the output a prefix of a match
     guide: Optional[object] = None
+    # 1..4 byte strings of 1..64 bytes (engine/streaming.py): the sequence finishes with "stop" at the first token
+    # after which one of them occurs in the output's bytes, and its content ends where that match starts
+    # (Sequence.stop_cut).  Sampling does not see it: up to the cut the output is the output without `stop`
+    stop: Optional[List[bytes]] = None
 
     @property
     def penalised(self) -> bool:
@@ -92,6 +96,14 @@ class Sequence:
     # guide's placement in the device arena (GuideTable.acquire; released when the sequence leaves)
     guide_state: Optional[object] = None
     guide_ref: Optional[object] = None
+    # params.stop: the scanner over the output's bytes (engine/streaming.py StopScanner), and once a stop string
+    # matched the byte offset where the content ends and the index of the string that matched there
+    stop_scan: Optional[object] = None
+    stop_cut: Optional[int] = None
+    stop_match: Optional[int] = None
+    # streaming: called on the engine thread after every step that settled a token of this sequence, with the
+    # sequence and the index in `output_ids` of its first newly settled token.  It must not block
+    on_tokens: Optional[Callable[["Sequence", int], None]] = None
 
     def __post_init__(self):
         seed = self.params.seed if self.params.seed is not None else random.getrandbits(64)

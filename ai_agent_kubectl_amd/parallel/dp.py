@@ -25,6 +25,7 @@ reconnect and it serves again.  Nothing is ever re-exec'ed in a process that tou
 from __future__ import annotations
 
 import asyncio
+import concurrent.futures
 import dataclasses
 import itertools
 import logging
@@ -41,6 +42,7 @@ from typing import Dict, List, Optional
 
 from ..llm.base import LLMBackend, LLMUnavailableError
 
+_PENDING = object()   # replica: a chat request whose guide is still compiling has no sequence yet
 FLUSH_EVERY = 16   # requests per engine-bound IPC message within one event-loop tick
 
 logger = logging.getLogger("app.dp")
@@ -246,6 +248,11 @@ def _replica_main(spec: ReplicaSpec, settings_dict: dict, authkey: bytes, parent
         eng.start()
         params = SamplingParams(max_new_tokens=s.MAX_NEW_TOKENS, ignore_eos=s.IGNORE_EOS, safe_decode=s.SAFE_DECODE)
         forced = forced_prefix(eng.tokenizer) if s.SAFE_DECODE else []
+        # chat requests go through the backend class the in-process deployment uses: one chat template, one guide
+        # LRU, one compile_guide
+        from ..llm.engine_backend import EngineLLM
+        llm = EngineLLM(eng, max_new_tokens=s.MAX_NEW_TOKENS, ignore_eos=s.IGNORE_EOS, safe_decode=s.SAFE_DECODE)
+        llm._started = True
         if os.path.exists(spec.address):
             os.unlink(spec.address)
         listener = Listener(spec.address, family="AF_UNIX", authkey=authkey)
@@ -298,10 +305,48 @@ def _replica_main(spec: ReplicaSpec, settings_dict: dict, authkey: bytes, parent
         with done_lock:
             done_buf.setdefault(key[0], []).append((key[1], (seq.output_ids, err, seq.finish_reason)))
 
+    # chat requests reply in events, batched the same way: per client {rid: [event, ...]}, one "chat_batch" message
+    # per engine step.  ("start", prompt tokens, jump-forward ids) and ("tok", ids, logprob records | None) for
+    # streaming requests, ("end", (output_ids, error, finish_reason, stop_cut, stop_match, n_forced, prompt tokens,
+    # logprob records | None)) for all; ("err", "client" | "unavailable", text) for a request that was not admitted
+    chat_buf: Dict[int, Dict[int, list]] = {}
+
+    def chat_event(key, ev):
+        with done_lock:
+            evs = chat_buf.setdefault(key[0], {}).setdefault(key[1], [])
+            if ev[0] == "tok" and evs and evs[-1][0] == "tok":   # steps that settled between two flushes
+                evs[-1][1].extend(ev[1])
+                if ev[2] is not None:
+                    evs[-1][2].extend(ev[2])
+            else:
+                evs.append(ev)
+
+    def chat_tokens(seq, first, key, begun):
+        if not begun:
+            begun.append(True)
+            chat_event(key, ("start", len(seq.prompt_ids) - seq.n_forced, seq.output_ids[:seq.n_forced]))
+        recs = None
+        if seq.params.logprobs is not None:
+            recs = [tuple(r) for r in seq.logprobs[first - seq.n_forced:]]
+        chat_event(key, ("tok", seq.output_ids[first:], recs))
+
+    def chat_done(seq, key, stream):
+        err = repr(seq.error) if seq.error is not None else None
+        recs = None
+        if not stream and seq.params.logprobs is not None:
+            recs = [tuple(r) for r in seq.logprobs]
+        chat_event(key, ("end", (seq.output_ids, err, seq.finish_reason, seq.stop_cut, seq.stop_match, seq.n_forced,
+                                 len(seq.prompt_ids) - seq.n_forced, recs)))
+
     last_obs = [0.0]
 
     def flush():
-        nonlocal done_buf
+        nonlocal done_buf, chat_buf
+        if chat_buf:
+            with done_lock:
+                cbufs, chat_buf = chat_buf, {}
+            for k, rows in cbufs.items():
+                send(k, ("chat_batch", spec.idx, list(rows.items())))
         now = time.perf_counter()
         if done_buf or now - last_obs[0] > 0.05:
             obs = eng.metrics.take()   # engine-level observations go to ONE client (counted once)
@@ -320,6 +365,33 @@ def _replica_main(spec: ReplicaSpec, settings_dict: dict, authkey: bytes, parent
     eng.step_end_hooks.append(flush)
 
     live: Dict[tuple, object] = {}
+    live_lock = threading.Lock()   # chat requests with a guide register their sequence from a worker thread
+    guide_pool = concurrent.futures.ThreadPoolExecutor(max_workers=2, thread_name_prefix="replica-guide")
+
+    def start_chat(key, payload):
+        """Admit one chat request: inline on the request loop, or on a `guide_pool` thread when it has a guide to
+        compile (neither the request loop nor the engine thread waits for a compilation)."""
+        messages, fields, stream = payload
+        try:
+            if not eng.healthy:
+                raise LLMUnavailableError(f"engine unhealthy: {eng.last_error}")
+            begun: list = []
+            seq, _ = llm.submit_chat(messages, lambda sq: chat_done(sq, key, stream),
+                                     (lambda sq, first: chat_tokens(sq, first, key, begun)) if stream else None,
+                                     **fields)
+        except Exception as e:   # a ValueError is the client's (HTTP 400), anything else this replica's (503)
+            with live_lock:
+                live.pop(key, None)
+            kind = "client" if isinstance(e, ValueError) else "unavailable"
+            send(key[0], ("chat_batch", spec.idx, [(key[1], [("err", kind, str(e))])]))
+            return
+        with live_lock:
+            gone = live.get(key) is not _PENDING
+            if not gone:
+                live[key] = seq
+        if gone:   # aborted, or its client left, while the guide compiled
+            eng.abort(seq)
+
     told_healthy: Dict[int, bool] = {}     # connection id -> the health last pushed to that client
     while True:
         with conns_lock:
@@ -348,8 +420,11 @@ def _replica_main(spec: ReplicaSpec, settings_dict: dict, authkey: bytes, parent
                     conns.pop(k, None)
                     send_locks.pop(k, None)
                 told_healthy.pop(k, None)
-                for key in [key for key in live if key[0] == k]:
-                    eng.abort(live.pop(key))
+                with live_lock:
+                    gone = [live.pop(key) for key in [key for key in live if key[0] == k]]
+                for seq in gone:
+                    if seq is not _PENDING:
+                        eng.abort(seq)
                 continue
             msgs = msg[2] if msg[0] == "batch" else [msg]
             for op, rid, payload in msgs:
@@ -362,9 +437,18 @@ def _replica_main(spec: ReplicaSpec, settings_dict: dict, authkey: bytes, parent
                         continue
                     seq = eng.submit(payload, params, lambda sq, key=key: done(sq, key), forced_prefix=forced)
                     live[key] = seq
+                elif op == "chat":
+                    with live_lock:
+                        live[key] = _PENDING
+                    if any(payload[1].get(f) for f in ("guided_regex", "guided_choice", "guided_json", "json_object")):
+                        guide_pool.submit(start_chat, key, payload)
+                    else:
+                        start_chat(key, payload)
                 elif op == "abort":
-                    if key in live:
-                        eng.abort(live.pop(key))
+                    with live_lock:
+                        seq = live.pop(key, None)
+                    if seq is not None and seq is not _PENDING:
+                        eng.abort(seq)
                 elif op == "hello":
                     cid_of[k] = int(payload or 0)
                     send(k, ("ready", spec.idx, cpus))
@@ -381,7 +465,9 @@ def _replica_main(spec: ReplicaSpec, settings_dict: dict, authkey: bytes, parent
                     send(k, ("ctl", rid, {"healthy": eng.healthy, "recoveries": eng.recoveries,
                                           "failures": eng.failures, "pid": os.getpid()}))
         if len(live) > 4096:
-            live = {key: v for key, v in live.items() if not v.finished}
+            with live_lock:
+                for key in [key for key, v in live.items() if v is not _PENDING and v.finished]:
+                    del live[key]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -659,6 +745,19 @@ class DPRouterLLM(LLMBackend):
                 self._publish_load(r)
             for loop, lst in by_loop.items():
                 loop.call_soon_threadsafe(_set_many, lst)
+        elif kind == "chat_batch":
+            by_loop = {}
+            with self._lock:
+                for rid, evs in b:
+                    final = evs[-1][0] in ("end", "err")
+                    ent = self._pending.pop(rid, None) if final else self._pending.get(rid)
+                    if ent is not None:
+                        if final:
+                            ent[2].inflight -= 1
+                        by_loop.setdefault(ent[0], []).append((ent[1], evs))
+                self._publish_load(r)
+            for loop, lst in by_loop.items():
+                loop.call_soon_threadsafe(_put_many, lst)
         elif kind == "ctl":
             with self._lock:
                 ent = self._pending.pop(a, None)
@@ -824,6 +923,104 @@ class DPRouterLLM(LLMBackend):
             raise LLMUnavailableError(err) if reason == "error" else RuntimeError(err)
         return self.tok.decode([t for t in out_ids if not self.tok.is_eos(t)])
 
+    # ---- OpenAI-compatible chat (api/openai_compat.py): EngineLLM's three methods, served by the replicas ----
+    async def _chat_events(self, messages, fields: dict, stream: bool):
+        """Route one chat request and yield the replica's event lists for it (one per engine step that had some),
+        ending with the list that holds its ("end", ...) or ("err", ...).  Leaving early (close, cancellation)
+        aborts the request in the replica."""
+        if not self._ready.is_set():
+            await self.start()
+        live = [r for r in self.replicas if r.up and r.healthy]
+        if not live:
+            raise LLMUnavailableError("no live DP replica")
+        rep = self._pick(live)
+        rid = next(self._ids)
+        loop = asyncio.get_running_loop()
+        q: asyncio.Queue = asyncio.Queue()
+        with self._lock:
+            self._pending[rid] = (loop, q, rep, "chat")
+            rep.inflight += 1
+            self._publish_load(rep)
+        self._send(rep, ("chat", rid, (messages, fields, stream)), loop)
+        ended = False
+        try:
+            while not ended:
+                evs = await q.get()
+                ended = evs[-1][0] in ("end", "err")
+                yield evs
+        finally:
+            if not ended:
+                try:
+                    self._send(rep, ("abort", rid, None), loop)
+                except Exception:
+                    pass
+                with self._lock:
+                    if self._pending.pop(rid, None) is not None:
+                        rep.inflight -= 1
+                        self._publish_load(rep)
+
+    async def _chat_result(self, messages, fields: dict, with_stop: bool):
+        from ..llm.engine_backend import assemble_chat
+        async for evs in self._chat_events(messages, fields, False):
+            ev = evs[-1]
+        if ev[0] == "err":
+            raise _chat_error(ev)
+        output_ids, err, reason, cut, match, n_forced, n_in, recs = ev[1]
+        if err is not None:
+            raise LLMUnavailableError(err)
+        res = assemble_chat(self.tok, output_ids, n_forced, recs, reason, cut, n_in)
+        return res + (match,) if with_stop else res
+
+    async def generate_chat(self, messages, max_tokens: int = 64, safe: bool = False, temperature: float = 0.0,
+                            top_p: float = 1.0, top_k: int = 0, seed: Optional[int] = None, with_stop: bool = False,
+                            **penalties):
+        """EngineLLM.generate_chat on the least-loaded replica: the same arguments, the same result."""
+        fields = _chat_fields(None, max_tokens, safe, temperature, top_p, top_k, seed, penalties)
+        res = await self._chat_result(messages, fields, with_stop)
+        return res[:4] + res[5:]
+
+    async def generate_chat_logprobs(self, messages, top_logprobs: int = 0, max_tokens: int = 64, safe: bool = False,
+                                     temperature: float = 0.0, top_p: float = 1.0, top_k: int = 0,
+                                     seed: Optional[int] = None, with_stop: bool = False, **penalties):
+        """EngineLLM.generate_chat_logprobs on the least-loaded replica."""
+        fields = _chat_fields(int(top_logprobs), max_tokens, safe, temperature, top_p, top_k, seed, penalties)
+        return await self._chat_result(messages, fields, with_stop)
+
+    async def stream_chat(self, messages, top_logprobs: Optional[int] = None, max_tokens: int = 64, safe: bool = False,
+                          temperature: float = 0.0, top_p: float = 1.0, top_k: int = 0, seed: Optional[int] = None,
+                          **penalties):
+        """EngineLLM.stream_chat on the least-loaded replica: the replica sends the ids (and logprob records) each
+        step settled, this process detokenises them."""
+        from ..llm.engine_backend import ChatStream
+        fields = _chat_fields(top_logprobs, max_tokens, safe, temperature, top_p, top_k, seed, penalties)
+        events = self._chat_events(messages, fields, True)
+        out = None
+        try:
+            async for evs in events:
+                last = evs[-1][0] == "end"
+                for ev in evs:
+                    if ev[0] == "err":
+                        raise _chat_error(ev)
+                    if ev[0] == "start":
+                        out = ChatStream(self.tok, fields.get("stop"), top_logprobs is not None, ev[2])
+                        yield {"prompt_tokens": ev[1]}
+                    elif ev[0] == "tok":
+                        ev = out.push(ev[1], ev[2], emit=not last)
+                        if ev is not None:
+                            yield ev
+                    else:
+                        output_ids, err, reason, _, _, n_forced, n_in, _ = ev[1]
+                        if err is not None:
+                            raise LLMUnavailableError(err)
+                        if out is None:   # finished without a settled token
+                            out = ChatStream(self.tok, fields.get("stop"), top_logprobs is not None,
+                                             output_ids[:n_forced])
+                            yield {"prompt_tokens": n_in}
+                        for ev in out.finish(reason, len(output_ids)):
+                            yield ev
+        finally:
+            await events.aclose()
+
 
 def _set_many(lst):
     for fut, val in lst:
@@ -837,5 +1034,27 @@ def _set(fut, val):
 
 
 def _set_exc(fut, exc):
-    if not fut.done():
+    if isinstance(fut, asyncio.Queue):   # a chat request: its consumer reads events
+        fut.put_nowait([("err", "unavailable", str(exc))])
+    elif not fut.done():
         fut.set_exception(exc)
+
+
+def _put_many(lst):
+    for q, evs in lst:
+        q.put_nowait(evs)
+
+
+def _chat_fields(top_logprobs, max_tokens, safe, temperature, top_p, top_k, seed, fields) -> dict:
+    """The wire form of a chat request's fields: EngineLLM.submit_chat's keyword arguments, plain values only."""
+    out = dict(fields, max_tokens=max_tokens, safe=safe, temperature=temperature, top_p=top_p, top_k=top_k,
+               seed=seed, logprobs=None if top_logprobs is None else int(top_logprobs))
+    if out.get("stop"):
+        out["stop"] = [bytes(x) for x in out["stop"]]
+    if out.get("logit_bias"):
+        out["logit_bias"] = {int(t): float(b) for t, b in out["logit_bias"].items()}
+    return out
+
+
+def _chat_error(ev):
+    return ValueError(ev[2]) if ev[1] == "client" else LLMUnavailableError(ev[2])
