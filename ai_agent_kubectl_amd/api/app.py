@@ -272,6 +272,12 @@ def create_app(settings: Optional[Settings] = None, backend: Any = _UNSET,
         except Exception:
             logger.exception("Failed to initialize LLM backend.")  # app.py:119-122
             backend = None
+    # LORA_KUBECTL: an unknown adapter name fails here, at start; an in-process engine backend is told the slot
+    # (replica processes read the same settings themselves)
+    from ..models.lora import kubectl_slot
+    slot = kubectl_slot(settings)
+    if slot is not None and hasattr(backend, "use_kubectl_adapter"):
+        backend.use_kubectl_adapter(slot)
     if backend is not None and hasattr(backend, "attach_metrics"):
         backend.attach_metrics(metrics)
     svc = KubectlService(settings, backend, metrics)

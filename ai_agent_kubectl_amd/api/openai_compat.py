@@ -175,9 +175,13 @@ _NEUTRAL = dict(presence_penalty=0.0, frequency_penalty=0.0, repetition_penalty=
 
 
 def install(app, svc, settings) -> None:
+    from ..models.lora import parse_adapters
     backend = svc.backend
     if backend is None or not hasattr(backend, "generate_chat"):
         return
+
+    # the LoRA adapters in slot order (models/lora.py): a request whose `model` names one runs on it
+    adapters = [name for name, _ in parse_adapters(getattr(settings, "LORA_ADAPTERS", ""))]
 
     def _auth(authorization: Optional[str], x_api_key: Optional[str]) -> None:
         key = settings.API_AUTH_KEY
@@ -190,7 +194,9 @@ def install(app, svc, settings) -> None:
     @app.get("/v1/models")
     async def list_models(authorization: Optional[str] = Header(None), x_api_key: Optional[str] = Header(None)):
         _auth(authorization, x_api_key)
-        return {"object": "list", "data": [{"id": settings.MODEL, "object": "model", "owned_by": "local"}]}
+        data = [{"id": settings.MODEL, "object": "model", "owned_by": "local"}]
+        data += [{"id": name, "object": "model", "owned_by": "local", "parent": settings.MODEL} for name in adapters]
+        return {"object": "list", "data": data}
 
     async def _stream(req: ChatRequest, request: Request, msgs, kw, head):
         """`stream: true`.  The backend's first event is awaited before the response starts, so a request that the
@@ -267,6 +273,8 @@ def install(app, svc, settings) -> None:
             kw["json_object"] = True
         elif fmt == "json_schema":
             kw["guided_json"] = req.response_format["json_schema"]["schema"]
+        if req.model in adapters:   # any other name: the base model, the name echoed
+            kw["adapter"] = adapters.index(req.model)
         if req.stop is not None:   # only when sent, like the penalties
             kw.update(stop=[s.encode("utf-8") for s in req.stop], with_stop=True)
         head = {"id": "chatcmpl-" + uuid.uuid4().hex[:24], "created": int(time.time()),

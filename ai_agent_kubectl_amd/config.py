@@ -120,6 +120,10 @@ class Settings:
     IGNORE_EOS: bool = False
     PREFIX_CACHING: bool = True
     MAX_NUM_BATCHED_TOKENS: int = 0     # 0: per model (ModelConfig.default_step_tokens)
+    # --- LoRA adapters served per request (models/lora.py) ---
+    LORA_ADAPTERS: str = ""              # name=dir[,name=dir...]: PEFT adapter directories, at most 8
+    MAX_LORA_RANK: int = 16              # padded rank of the device layout: 16 | 32 | 64
+    LORA_KUBECTL: str = ""               # adapter name /kubectl-command generations run on ("" = the base model)
     FAULT_LLM_DELAY_MS: int = 0
     FAULT_LLM_ERROR: str = ""
     # --- multi-worker HTTP tier (serve.py) ---

@@ -16,6 +16,7 @@ from typing import Optional
 import torch
 
 from ..models.config import get_config
+from ..models.lora import load_adapters
 from ..models.weights import ParallelInfo, build_weights
 from .engine import LLMEngine
 from .runner import ModelRunner
@@ -45,6 +46,8 @@ class EngineOptions:
     ignore_eos: bool = False
     prefix_caching: bool = True
     guide_states: int = 8192       # DFA states of the guided-decoding arena (512 bytes each; engine/guided.py)
+    lora_adapters: str = ""        # LORA_ADAPTERS: name=dir[,name=dir...] (models/lora.py)
+    max_lora_rank: int = 16        # MAX_LORA_RANK: 16 | 32 | 64
 
     @classmethod
     def from_settings(cls, s) -> "EngineOptions":
@@ -56,6 +59,7 @@ class EngineOptions:
                    kv_cache_tokens=int(os.environ.get("KV_CACHE_TOKENS", 0)),
                    max_model_len=int(os.environ.get("MAX_MODEL_LEN", 8192)),
                    guide_states=int(os.environ.get("GUIDE_STATES", 8192)),
+                   lora_adapters=s.LORA_ADAPTERS, max_lora_rank=s.MAX_LORA_RANK,
                    device="cuda" if torch.cuda.is_available() else "cpu")
 
 
@@ -76,6 +80,8 @@ def build_engine(opts: EngineOptions, comm=None, metrics=None) -> LLMEngine:
     if cfg.is_moe and opts.ep_size not in (1, opts.tp_size):
         raise ValueError("EP must equal TP (experts are sharded over the tensor-parallel group)")
     par = ParallelInfo(opts.tp_rank, opts.tp_size, opts.tp_rank if ep_size > 1 else 0, ep_size)
+    # LoRA adapters: read and checked before the weights are built, so a refusal costs nothing
+    lora = load_adapters(opts.lora_adapters, cfg, opts.max_lora_rank, device=dev, tp_size=opts.tp_size, dtype=dtype)
     weights = build_weights(opts.weights, cfg, par, device=dev, dtype=dtype)
     # ---- KV pool size ----
     per_block = cfg.num_layers * 2 * (cfg.num_kv_heads // opts.tp_size) * cfg.head_dim * opts.block_size * 2
@@ -110,6 +116,7 @@ def build_engine(opts: EngineOptions, comm=None, metrics=None) -> LLMEngine:
                          comm=comm, tp_rank=opts.tp_rank, tp_size=opts.tp_size, ep_rank=par.ep_rank,
                          ep_size=ep_size, use_graphs=opts.use_graphs, tokenizer=tok,
                          guide_states=opts.guide_states)
+    runner.model.lora = lora
     step_tokens = opts.max_batched_tokens if opts.max_batched_tokens > 0 else cfg.default_step_tokens()
     eng = LLMEngine(runner, tok, max_batch=opts.max_batch, max_batched_tokens=step_tokens,
                     max_model_len=opts.max_model_len, prefix_caching=opts.prefix_caching, metrics=metrics)

@@ -158,6 +158,12 @@ class LLMEngine:
         except Exception:  # pragma: no cover
             pass
 
+    @property
+    def lora_names(self) -> List[str]:
+        """The loaded LoRA adapters in slot order (SamplingParams.adapter indexes this list)."""
+        ls = getattr(self.runner.model, "lora", None)
+        return list(ls.names) if ls is not None else []
+
     def submit(self, prompt_ids: List[int], params: SamplingParams, callback: Callable[[Sequence], None],
                forced_prefix: Optional[List[int]] = None,
                on_tokens: Optional[Callable[[Sequence, int], None]] = None) -> Sequence:
@@ -171,6 +177,10 @@ class LLMEngine:
             if self.runner.tp_size > 1:
                 # the logits are vocab-parallel: the ranks' (max, mass) pairs would have to be combined
                 raise ValueError("logprobs are not supported with tensor parallelism (TP > 1)")
+        if params.adapter is not None:
+            n = len(self.lora_names)
+            if isinstance(params.adapter, bool) or not isinstance(params.adapter, int) or not 0 <= params.adapter < n:
+                raise ValueError(f"adapter {params.adapter!r} is outside the {n} loaded LoRA adapters")
         validate_stops(params.stop)
         penalties.validate(params, self.runner.cfg.vocab_size, self.runner.tp_size)
         guided.validate(params, self.tokenizer, self.runner.tp_size, forced_prefix)
@@ -367,7 +377,7 @@ class LLMEngine:
             if s.finished:
                 continue
             if id(s) in batch.partial:   # a chunk of a long prompt: its KV is cached, nothing sampled
-                self.bm.register_computed(s.block_table, s.all_ids[:s.num_computed], s.block_hashes)
+                self.bm.register_computed(s.block_table, s.cache_ids[:s.num_computed], s.block_hashes)
                 continue
             if s.ph_row is None:   # not advanced (finished before the advance)
                 continue
@@ -380,7 +390,7 @@ class LLMEngine:
                 s.logprobs.append(TokenLogprob(float(recs.logprob[row]), recs.top_ids[row, :k].tolist(),
                                                recs.top_logprobs[row, :k].tolist()))
             if id(s) in prefill:
-                self.bm.register_computed(s.block_table, s.all_ids[:s.num_computed], s.block_hashes)
+                self.bm.register_computed(s.block_table, s.cache_ids[:s.num_computed], s.block_hashes)
                 if s.t_first_token is None:
                     s.t_first_token = now
                     if m is not None:

@@ -178,6 +178,10 @@ class ModelRunner:
         # ... and the stack image of a step with a row under a stack guide (JSON mode, _stage_guide_stacks)
         self._h_gss: List[Optional[torch.Tensor]] = [None, None]
         self._sflip = 0
+        # LoRA (models/lora.py): the per-row adapter slots of a step with at least one adapter row go to the device
+        # through two pinned buffers like the sampling image (_stage_adapter); a step without one touches neither
+        self._h_ads: List[Optional[torch.Tensor]] = [None, None]
+        self._aflip = 0
         # the records of the step read back last (collect / execute), for engine._settle to take
         self.last_logprobs: Optional[StepLogprobs] = None
         self.d_hdr = torch.zeros(HDR, dtype=torch.int32, device=self.device)
@@ -197,7 +201,8 @@ class ModelRunner:
         self.graph_pool = None
         self.stats = {"decode_steps": 0, "prefill_steps": 0, "graph_replays": 0, "decode_ms": 0.0,
                       "prefill_ms": 0.0, "prefill_tokens": 0, "persistent_stalls": 0, "sampled_steps": 0,
-                      "logprob_steps": 0, "penalty_steps": 0, "guided_steps": 0, "json_steps": 0}
+                      "logprob_steps": 0, "penalty_steps": 0, "guided_steps": 0, "json_steps": 0,
+                      "lora_steps": 0}
         # bucket -> the captured graph holds the persistent decode kernel (its error word must be read
         # back on every replay of that graph, whatever model.persistent says now)
         self.graph_persistent: Dict[int, bool] = {}
@@ -214,15 +219,47 @@ class ModelRunner:
     def _cascade(self, B: int) -> bool:
         return self.cascade_min_b > 0 and B >= self.cascade_min_b and self.device.type == "cuda"
 
-    def _decode_forward(self, B: int, samp: Optional[SampleArrays] = None) -> None:
+    def _decode_forward(self, B: int, samp: Optional[SampleArrays] = None,
+                        adapter: Optional[torch.Tensor] = None) -> None:
         meta = AttnMeta(positions=self._view("pos", B), slot_mapping=self._view("slots", B),
                         block_tables=self._view("bt", B), ctx_lens=self._view("ctx", B),
                         logits_indices=self.d_logits_idx[:B], is_decode=True,
-                        shared_blocks=self._view("nsh", 1) if self._cascade(B) else None)
+                        shared_blocks=self._view("nsh", 1) if self._cascade(B) else None, adapter=adapter)
         h = self.model.forward(self._view("ids", B), meta, self.k_cache, self.v_cache)
         mask_idx = self._view("mask", B) if self.mask_bits is not None else None
         tok = self.model.sample(h, self.mask_bits, mask_idx, samp)
         self.d_out[:B].copy_(tok)
+
+    def _stage_adapter(self, batch: Batch, rows: int, num_query: Optional[List[int]] = None) -> Optional[torch.Tensor]:
+        """The step's LoRA slot per token row on the device (int32 [rows]: a sequence's slot repeated over its
+        query rows, -1 for base requests and padding rows), or None when no request of `batch` runs on an
+        adapter: that step takes its usual route untouched.  The slot is static per sequence, so chained and
+        lookahead steps need no fix-up on the device."""
+        slots = [s.params.adapter for s in batch.seqs]
+        if all(a is None for a in slots):
+            return None
+        if self.model.lora is None:
+            raise RuntimeError("a request names a LoRA adapter but the engine has none loaded")
+        if self.tp_size > 1:
+            raise RuntimeError("LoRA adapters are not wired through the TP worker protocol")
+        self.stats["lora_steps"] += 1
+        per_seq = np.asarray([-1 if a is None else int(a) for a in slots], dtype=np.int32)
+        img = np.full(rows, -1, dtype=np.int32)
+        if num_query is None:
+            img[:len(per_seq)] = per_seq
+        else:
+            flat = np.repeat(per_seq, np.asarray(num_query, dtype=np.int64))
+            img[:flat.shape[0]] = flat
+        if self.device.type != "cuda":
+            return torch.from_numpy(img)
+        k = self._aflip = self._aflip ^ 1
+        hb = self._h_ads[k]
+        if hb is None or hb.numel() < rows:
+            hb = torch.empty(max(rows, 2 * (hb.numel() if hb is not None else 0), self.bmax), dtype=torch.int32,
+                             pin_memory=True)
+            self._h_ads[k] = hb
+        hb.numpy()[:rows] = img
+        return hb[:rows].to(self.device, non_blocking=True)
 
     # ---- steps that need the logits written: a request with temperature > 0, with logprobs, or with
     # penalties / logit_bias ----
@@ -537,12 +574,15 @@ class ModelRunner:
             for row, src in fix:
                 pend[row] = src
         samp = self._stage_samp(batch, Bp, ahead=1 if chained else 0, pend=pend)
-        self._launch_decode(Bp, n_copy, samp)
+        adapter = self._stage_adapter(batch, Bp)
+        self._launch_decode(Bp, n_copy, samp, adapter)
         ho[:B].copy_(self.d_out[:B], non_blocking=True)
         lh, ln = self._copy_logprobs(samp, B, self._h_lps, k)
         # a sampled step ran eagerly beside the bucket's graph: the model's current setting decides
         # whether it launched the persistent kernel, not what the graph was captured with
-        eh = self._copy_err(persistent=self._persistent_step(Bp) if samp is None else self.model.persistent_ok(Bp))
+        eager = samp is not None or adapter is not None
+        eh = self._copy_err(persistent=self._persistent_step(Bp) if not eager
+                            else adapter is None and self.model.persistent_ok(Bp))
         ev = None
         if self.device.type == "cuda":
             ev = torch.cuda.Event()
@@ -576,8 +616,9 @@ class ModelRunner:
         pend = [s.ph_row if s.ph_row is not None and s.num_computed + nq == s.total_len else -1
                 for s, nq in zip(batch.seqs, batch.num_query)] if nf else None
         samp = self._stage_samp(batch, S, pend=pend)
+        adapter = self._stage_adapter(batch, T, batch.num_query)
         try:
-            tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens, samp)
+            tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens, samp, adapter)
         finally:
             self.model.mark_layer = -1
         progress, self.model.mark_event = self.model.mark_event, None
@@ -698,13 +739,16 @@ class ModelRunner:
         self.stats["decode_steps"] += 1
         return ho[:B].tolist()
 
-    def _launch_decode(self, Bp: int, n_copy: int, samp: Optional[SampleArrays] = None) -> None:
+    def _launch_decode(self, Bp: int, n_copy: int, samp: Optional[SampleArrays] = None,
+                       adapter: Optional[torch.Tensor] = None) -> None:
         if self.tp_size > 1:
             self.comm.broadcast(self.d_stage[:n_copy], src=0)
-        # the captured graphs end in the greedy sampler: a step with a sampling request runs eagerly
-        g = self.graphs.get(Bp) if samp is None else None
-        if samp is not None:
-            self._decode_forward(Bp, samp)
+        # the captured graphs end in the greedy sampler and hold the base model's route: a step with a sampling
+        # request or with LoRA rows runs eagerly
+        eager = samp is not None or adapter is not None
+        g = self.graphs.get(Bp) if not eager else None
+        if eager:
+            self._decode_forward(Bp, samp, adapter)
         elif g is not None:
             g.replay()
             self.stats["graph_replays"] += 1
@@ -792,7 +836,8 @@ class ModelRunner:
         return (buf, nf) if with_fix else buf
 
     def _run_prefill(self, buf: torch.Tensor, T: int, S: int, max_q: int, nc: int = 0, nd: int = 0,
-                     t_real: int = 0, samp: Optional[SampleArrays] = None) -> torch.Tensor:
+                     t_real: int = 0, samp: Optional[SampleArrays] = None,
+                     adapter: Optional[torch.Tensor] = None) -> torch.Tensor:
         mb = self.max_blocks
         if nc:
             n = buf.shape[0]
@@ -806,7 +851,7 @@ class ModelRunner:
         bt = buf[o:o + S * mb].view(S, mb)
         meta = AttnMeta(positions=pos, slot_mapping=slots, block_tables=bt, ctx_lens=ctx, logits_indices=lidx,
                         is_decode=False, q_starts=q_starts, max_q_len=max_q, num_decode=nd,
-                        num_tokens=t_real or T)
+                        num_tokens=t_real or T, adapter=adapter)
         h = self.model.forward(ids, meta, self.k_cache, self.v_cache)
         return self.model.sample(h, self.mask_bits, mask if self.mask_bits is not None else None, samp)
 
@@ -850,7 +895,7 @@ class ModelRunner:
             self._bcast_header(KIND_DECODE, Bp, n_copy)
             self.d_stage[:n_copy].copy_(self.h_stage[:n_copy], non_blocking=True)
             samp = self._stage_samp(batch, Bp)
-            self._launch_decode(Bp, n_copy, samp)
+            self._launch_decode(Bp, n_copy, samp, self._stage_adapter(batch, Bp))
             self.h_out[:B].copy_(self.d_out[:B], non_blocking=True)
             eh = self._copy_err()
             if self.device.type == "cuda":
@@ -869,7 +914,8 @@ class ModelRunner:
         if self.tp_size > 1:
             self.comm.broadcast(buf, src=0)
         samp = self._stage_samp(batch, S)
-        tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens, samp)
+        tok = self._run_prefill(buf, T, S, max_q, nc, nd, batch.num_tokens, samp,
+                                self._stage_adapter(batch, T, batch.num_query))
         eh = self._copy_err()
         out = tok.cpu().tolist()
         self._check_err(eh)

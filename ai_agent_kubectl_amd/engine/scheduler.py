@@ -145,10 +145,10 @@ class Scheduler:
         while self.waiting and budget > 0 and n_busy + len(admitted) - n_cont < self.max_batch:
             seq = self.waiting[0]
             try:
-                table, cached, hashes = self.bm.allocate_prompt(seq.all_ids)
+                table, cached, hashes = self.bm.allocate_prompt(seq.cache_ids)
             except NoFreeBlocks:
                 break
-            part = self.bm.reuse_partial(table, seq.all_ids, cached, hashes) if self.partial_reuse else None
+            part = self.bm.reuse_partial(table, seq.cache_ids, cached, hashes) if self.partial_reuse else None
             q = seq.total_len - cached - (part[1] if part else 0)
             c = q
             if q > budget:

@@ -14,6 +14,7 @@ _ids = itertools.count()
 # one is in flight (engine._lookahead_step) appends it; the readback replaces it, and until then the
 # next step's packed inputs take that token from the device (runner fixups)
 PLACEHOLDER = -1
+ADAPTER_TAG_SHIFT = 20   # Sequence.cache_ids
 
 
 class SeqStatus(enum.Enum):
@@ -50,6 +51,9 @@ class SamplingParams:
     # after which one of them occurs in the output's bytes, and its content ends where that match starts
     # (Sequence.stop_cut).  Sampling does not see it: up to the cut the output is the output without `stop`
     stop: Optional[List[bytes]] = None
+    # the LoRA adapter the request runs on: its slot among the engine's loaded adapters (models/lora.py), None = the
+    # base model.  Static for the sequence's life
+    adapter: Optional[int] = None
 
     @property
     def penalised(self) -> bool:
@@ -122,6 +126,17 @@ class Sequence:
     @property
     def all_ids(self) -> List[int]:
         return self.prompt_ids + self.output_ids[self.n_forced:]
+
+    @property
+    def cache_ids(self) -> List[int]:
+        """all_ids as the prefix cache sees them: KV computed under an adapter must never be shared with the base
+        model or another adapter, so adapter a's ids carry the tag (a + 1) << 20 (the vocabulary is below 2**20:
+        models/lora.py load_adapters refuses a larger one)."""
+        a = self.params.adapter
+        if a is None:
+            return self.all_ids
+        tag = (int(a) + 1) << ADAPTER_TAG_SHIFT
+        return [t + tag for t in self.all_ids]
 
     @property
     def total_len(self) -> int:

@@ -48,6 +48,7 @@ class EngineLLM(LLMBackend):
     @classmethod
     def from_settings(cls, settings, metrics=None) -> "EngineLLM":
         from ..engine.builder import EngineOptions, build_engine
+        from ..models.lora import kubectl_slot
 
         opts = EngineOptions.from_settings(settings)
         comm = None
@@ -60,8 +61,16 @@ class EngineLLM(LLMBackend):
         eng = build_engine(opts, comm=comm, metrics=metrics)
         if opts.use_graphs and opts.device.startswith("cuda"):
             eng.runner.capture_graphs()
-        return cls(eng, max_new_tokens=settings.MAX_NEW_TOKENS, ignore_eos=settings.IGNORE_EOS,
-                   safe_decode=settings.SAFE_DECODE)
+        llm = cls(eng, max_new_tokens=settings.MAX_NEW_TOKENS, ignore_eos=settings.IGNORE_EOS,
+                  safe_decode=settings.SAFE_DECODE)
+        llm.use_kubectl_adapter(kubectl_slot(settings))
+        return llm
+
+    def use_kubectl_adapter(self, slot: Optional[int]) -> None:
+        """LORA_KUBECTL: /kubectl-command generations (`generate`) run on this adapter slot (None: the base model)."""
+        if slot is not None and not 0 <= slot < len(self.engine.lora_names):
+            raise ValueError(f"LORA_KUBECTL: slot {slot} is outside the engine's {len(self.engine.lora_names)} adapters")
+        self.params.adapter = slot
 
     def prompt_ids(self, query: str) -> List[int]:
         return self._prefix_ids + self.tok.encode(query + PROMPT_SUFFIX) + self._after_ids
@@ -255,14 +264,14 @@ class EngineLLM(LLMBackend):
 
     def chat_params(self, max_tokens, safe, temperature, top_p, top_k, seed, logprobs, guide=None,
                     presence_penalty: float = 0.0, frequency_penalty: float = 0.0, repetition_penalty: float = 1.0,
-                    logit_bias=None, stop=None) -> SamplingParams:
+                    logit_bias=None, stop=None, adapter: Optional[int] = None) -> SamplingParams:
         return SamplingParams(max_new_tokens=max_tokens, ignore_eos=False, safe_decode=safe,
                               temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=seed,
                               logprobs=logprobs, presence_penalty=float(presence_penalty),
                               frequency_penalty=float(frequency_penalty),
                               repetition_penalty=float(repetition_penalty),
                               logit_bias={int(t): float(b) for t, b in logit_bias.items()} if logit_bias else None,
-                              guide=guide, stop=[bytes(x) for x in stop] if stop else None)
+                              guide=guide, stop=[bytes(x) for x in stop] if stop else None, adapter=adapter)
 
     def submit_chat(self, messages, done, on_tokens, max_tokens, safe, temperature, top_p, top_k, seed, logprobs,
                     guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None,

@@ -50,6 +50,7 @@ class AttnMeta:
     num_decode: int = 0                # mixed step: the first num_decode sequences are 1-token decode rows
     num_tokens: int = 0                # real tokens when the step is padded (rows beyond are padding)
     shared_blocks: Optional[torch.Tensor] = None   # decode: [1] leading blocks shared by every row (cascade)
+    adapter: Optional[torch.Tensor] = None    # [T] LoRA slot per token row (-1 = base model); None: no adapter rows
 
 
 SAMP_WORDS = 6   # int32 words per row of a packed sampling image
@@ -204,6 +205,8 @@ class LlamaModel:
         self.persistent_max_b = int(os.environ.get("KA_PERSISTENT_MAX_B", "2"))
         self._pd_max_b = None
         self.persistent_stamps = None   # diagnostics: int64 [CUs, L, 16] phase timestamps (scripts/)
+        # the resident LoRA adapters (models/lora.py LoraSet, set by engine/builder.py); None: none configured
+        self.lora = None
 
     def _layer(self, i):
         p = f"layers.{i}."
@@ -218,6 +221,8 @@ class LlamaModel:
         h = ops.embedding(input_ids, self.W["embed"])
         if ops.reference_fp32():   # test-only fp32 truth: activations / residual in fp32 (ops.force_reference)
             h = h.float()
+        if meta.adapter is not None:   # a step with LoRA rows: the plain route, nothing below runs
+            return self._forward_lora(h, meta, k_cache, v_cache)
         if meta.is_decode and not ops._ref(h) and self.persistent_ok(input_ids.shape[0]):
             return self._forward_persistent(h, meta, k_cache, v_cache)
         residual = None
@@ -300,6 +305,45 @@ class LlamaModel:
         # prefill: only the sequences' last rows are sampled, so only they are normed
         idx = meta.logits_indices
         return ops.rmsnorm(h.index_select(0, idx), self.W["norm"], eps, residual=residual.index_select(0, idx))
+
+    def _lora_add(self, y: torch.Tensor, x: torch.Tensor, li: int, w: str, adapter: torch.Tensor) -> torch.Tensor:
+        f = self.lora.layers[li][w]
+        return ops.lora_add(y, x, adapter, f.A, f.B, f.scale, f.seg)
+
+    def _forward_lora(self, h: torch.Tensor, meta: AttnMeta, k_cache: torch.Tensor,
+                      v_cache: torch.Tensor) -> torch.Tensor:
+        """`forward` for a step with LoRA rows (meta.adapter): every projection as a resolved bf16 GEMM followed by
+        ops.lora_add on its output, which leaves the rows of -1 as they are.  No deferred split-K reductions, no
+        SwiGLU epilogue, no persistent kernel, no last-layer pruning: base rows sharing the step may therefore
+        differ from their usual route at bf16 near-ties."""
+        if self.lora is None or self.tp_size != 1 or self.cfg.is_moe:
+            raise RuntimeError("a step carries LoRA rows but the model has no adapters (dense models, TP = 1)")
+        eps, ad = self.cfg.norm_eps, meta.adapter
+        T = h.shape[0]
+        residual = None
+        for li, L in enumerate(self.layers):
+            if li == self.mark_layer and h.is_cuda:   # progress marker (engine lookahead timing)
+                self.mark_event = torch.cuda.Event()
+                self.mark_event.record()
+            if residual is None:
+                residual = h
+                x = ops.rmsnorm(h, L["ln1"], eps)
+            else:
+                x = ops.rmsnorm(h, L["ln1"], eps, residual=residual)
+            qkv = self._lora_add(ops.linear(x, L["wqkv"]), x, li, "wqkv", ad)
+            q = ops.rope_kv_write(qkv, meta.positions, self.cos_sin, meta.slot_mapping, k_cache[li], v_cache[li],
+                                  self.hq, self.hkv, self.D)
+            a = self._attention(q, meta, k_cache[li], v_cache[li])
+            if 0 < meta.num_tokens < T and not meta.is_decode:
+                a[meta.num_tokens:].zero_()   # padding rows: no sequence's attention writes them
+            a = a.reshape(T, self.hq * self.D)
+            h = self._lora_add(ops.linear(a, L["wo"]), a, li, "wo", ad)
+            x = ops.rmsnorm(h, L["ln2"], eps, residual=residual)
+            gu = self._lora_add(ops.linear(x, L["w13"]), x, li, "w13", ad)
+            g = ops.silu_mul(gu)
+            h = self._lora_add(ops.linear(g, L["w2"]), g, li, "w2", ad)
+        x = ops.rmsnorm(h, self.W["norm"], eps, residual=residual)
+        return x if meta.is_decode else x.index_select(0, meta.logits_indices)
 
     def persistent_ok(self, B: int = 1) -> bool:
         """The persistent all-layers kernel takes a decode step of B sequences: B <= KA_PERSISTENT_MAX_B

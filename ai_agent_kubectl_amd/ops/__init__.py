@@ -611,6 +611,61 @@ def guide_mask_stack(table: TokenTable, arena_trans: torch.Tensor, arena_accept:
     return bits, idx, after, depth_after, stack_after
 
 
+LORA_RANKS = (16, 32, 64)   # padded ranks csrc/lora.hip is built for
+LORA_MAX_ADAPTERS = 8
+_LORA_WS: dict = {}         # device -> fp32 workspace (grown on demand; one stream uses it at a time)
+_LORA_SEG: dict = {}        # boundaries -> the host int array the launcher reads
+
+
+def lora_add(y: torch.Tensor, x: torch.Tensor, row_adapter: torch.Tensor, A: torch.Tensor, B: torch.Tensor,
+             scale: torch.Tensor, seg) -> torch.Tensor:
+    """In place y += scale * (x A^T) B^T with the adapter chosen per row (csrc/lora.hip; semantics:
+    ops/reference.py `lora_add`).  y bf16 [T, N], x bf16 [T, K], row_adapter int32 [T] (-1: no adapter),
+    A bf16 [n_adapters, S, R, K], B bf16 [n_adapters, N, R], scale fp32 [n_adapters, S]; seg: the S + 1
+    boundaries of the S stacked sub-modules in N (host integers: a sequence or a CPU tensor), multiples of 16.
+    K % 64 == 0, N % 16 == 0, R in LORA_RANKS."""
+    if _ref(y):
+        return ref.lora_add(y, x, row_adapter, A, B, scale, seg)
+    lib = require()
+    dev = y.device
+    if y.dim() != 2 or x.dim() != 2 or A.dim() != 4 or B.dim() != 3 or scale.dim() != 2:
+        raise ValueError("lora_add: y [T, N], x [T, K], A [n, S, R, K], B [n, N, R], scale [n, S]")
+    T, N = y.shape
+    K = x.shape[1]
+    n, S, R = A.shape[0], A.shape[1], A.shape[2]
+    for name, t, dt in (("y", y, torch.bfloat16), ("x", x, torch.bfloat16), ("A", A, torch.bfloat16),
+                        ("B", B, torch.bfloat16), ("scale", scale, torch.float32),
+                        ("row_adapter", row_adapter, torch.int32)):
+        if t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"lora_add: {name} must be a contiguous {dt} tensor on {dev}")
+    if x.shape[0] != T or row_adapter.shape != (T,) or A.shape[3] != K or B.shape != (n, N, R) \
+            or scale.shape != (n, S):
+        raise ValueError("lora_add: shapes disagree (y [T, N], x [T, K], row_adapter [T], A [n, S, R, K], "
+                         "B [n, N, R], scale [n, S])")
+    if T == 0:
+        return y
+    key = tuple(int(v) for v in seg)
+    if len(key) != S + 1:
+        raise ValueError(f"lora_add: seg must hold {S + 1} boundaries")
+    hseg = _LORA_SEG.get(key)
+    if hseg is None:
+        import ctypes
+        hseg = _LORA_SEG[key] = (ctypes.c_int * len(key))(*key)
+    need = int(lib.ka_lora_splits(T, S, K)) * T * S * R
+    ws = _LORA_WS.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _LORA_WS[dev] = torch.empty(max(need, 1 << 16), dtype=torch.float32, device=dev)
+    check(lib.ka_lora_add(_p(y), _p(x), _p(row_adapter), _p(A), _p(B), _p(scale), hseg, _p(ws), T, N, K, S, R, n,
+                          _stream()), "lora_add")
+    return y
+
+
+def lora_geometry() -> Tuple[int, int]:
+    """(rows per tile, columns per expand workgroup) of csrc/lora.hip: what the tests straddle."""
+    lib = require()
+    return int(lib.ka_lora_tile_rows()), int(lib.ka_lora_tile_n())
+
+
 def argmax_combine(vals: torch.Tensor, idxs: torch.Tensor) -> torch.Tensor:
     """TP vocab-parallel greedy combine: vals / idxs [ranks, S] (every rank's best value and global token
     id) -> [S] int32 id of the largest value, the lowest id on ties (csrc/sampling.hip)."""

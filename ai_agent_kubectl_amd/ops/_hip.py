@@ -65,6 +65,10 @@ _SIGS = {
     "ka_guide_mask_tile": [],
     "ka_guide_mask_stack": [P, P, P, P, P, P, P, I, I, I, P, P, P, I, P, P, P, P, P, P, P, P, I, P, P, I, I, P],
     "ka_guide_mask_stack_tile": [],
+    "ka_lora_add": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
+    "ka_lora_tile_rows": [],
+    "ka_lora_tile_n": [],
+    "ka_lora_splits": [I, I, I],
     "ka_moe_topk": [P, P, P, I, I, I, P],
     "ka_paged_decode": [P, P, P, P, P, I, P, I, I, I, I, I, F, P],
     "ka_paged_decode_rope": [P, P, P, I, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, P],

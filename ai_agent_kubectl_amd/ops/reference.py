@@ -671,3 +671,29 @@ def guide_mask_stack(table, arena_trans, arena_accept, arena_pop, row_base, row_
     return (torch.from_numpy(bits.view(np.int32)).to(dev), torch.from_numpy(idx).to(dev),
             torch.from_numpy(after).to(dev), torch.from_numpy(depth_after).to(dev),
             torch.from_numpy(stack_after.view(np.int32)).to(dev))
+
+
+def lora_add(y, x, row_adapter, A, B, scale, seg):
+    """Per-row LoRA (csrc/lora.hip): in place y[i] += scale[a, s] * (x[i] A[a, s]^T) B[a, seg[s]:seg[s + 1]]^T
+    for a = row_adapter[i] >= 0.  y [T, N], x [T, K], row_adapter int32 [T] (-1: the row has no adapter),
+    A [n_adapters, S, R, K], B [n_adapters, N, R], scale fp32 [n_adapters, S], seg the S + 1 segment boundaries
+    of N.  t = x A^T is accumulated in fp32 and rounded to bf16 (part of the definition: the expand step runs on
+    the bf16 MFMA), t B^T is accumulated in fp32, and y is rounded once.  Rows of -1 and segments of scale 0 keep
+    their bits."""
+    seg = [int(v) for v in seg]
+    ra = row_adapter.long().cpu()
+    sc_h = scale.float().cpu()
+    for a in sorted(set(ra.tolist())):
+        if a < 0 or a >= A.shape[0]:
+            continue
+        rows = (ra == a).nonzero().flatten().to(y.device)
+        xf = x.index_select(0, rows).float()
+        for s in range(len(seg) - 1):
+            sc = float(sc_h[a, s])
+            if sc == 0.0:
+                continue
+            t = (xf @ A[a, s].float().T).to(torch.bfloat16).float()
+            d = t @ B[a, seg[s]:seg[s + 1]].float().T
+            cur = y[:, seg[s]:seg[s + 1]].index_select(0, rows).float()
+            y[:, seg[s]:seg[s + 1]].index_copy_(0, rows, (cur + sc * d).to(y.dtype))
+    return y

@@ -246,7 +246,9 @@ def _replica_main(spec: ReplicaSpec, settings_dict: dict, authkey: bytes, parent
         from ..utils.runtime import tune_gc
         tune_gc()
         eng.start()
-        params = SamplingParams(max_new_tokens=s.MAX_NEW_TOKENS, ignore_eos=s.IGNORE_EOS, safe_decode=s.SAFE_DECODE)
+        from ..models.lora import kubectl_slot
+        params = SamplingParams(max_new_tokens=s.MAX_NEW_TOKENS, ignore_eos=s.IGNORE_EOS, safe_decode=s.SAFE_DECODE,
+                                adapter=kubectl_slot(s))
         forced = forced_prefix(eng.tokenizer) if s.SAFE_DECODE else []
         # chat requests go through the backend class the in-process deployment uses: one chat template, one guide
         # LRU, one compile_guide
